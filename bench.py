@@ -6,8 +6,13 @@ N = 1 (default): configuration C3.  One step = one frame of the
 frame prepass + unit cull + integrate kernel) over the whole 512^3 volume, inputs resident
 in HBM; value = voxels of the volume x frames / wall time of the K timed steps (the
 KinectFusion "voxel updates" convention: every voxel is visited per frame, dead units by
-the culler).  Extra objects of the same line:
-  roofline      the integrate kernel: algorithmic bytes (the reference's types, §8d) per
+the culler).  A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the line with that figure and `ms_per_step` alone; `--dump-outputs DIR` also
+writes the volume state the last timed step left (dump_outputs: a fixed sample, float32 .npy;
+same arguments, same inputs, so two builds compare array for array).  `--full` adds to the
+same line:
+  roofline      the integrate kernel (the K steps again with kernel events, and once more
+                counting voxels): algorithmic bytes (the reference's types, §8d) per
                 launch / its HIP-event duration, against 8 TB/s; traffic = PMC bytes of the
                 same kernel binary (stamped by library hash, tools/traffic.py), else null;
   pipeline      §8d frames/s of C3: per frame the host TUM pose path (groundtruth lines ->
@@ -284,10 +289,47 @@ def resident_frames(frames, with_mask=True, ids=False):
     return dbuf, rbuf, mbuf
 
 
-def timed_integrate(vol, step, K, warmup, pg=None, device=0, finish=None):
+def dump_outputs(vol, out_dir, max_bytes=48_000_000, seed=0):
+    """What a caller of the timed step holds after the last timed step, the volume's state, as
+    out_dir/{sdf,wt,color,hist}.npy in float32 (weights and counts far below 2^24, so exact).
+    A fixed sample of the volume in the reference layout: sdf, weight and colour on up to 8 whole
+    x-planes spread evenly over the local volume, the 32-bin histogram on a seeded choice of
+    voxels of each of those planes, sized to stay under max_bytes in all."""
+    from semtsdf import _lib as L
+
+    Dx, Dy, Dz = (int(v) for v in vol.local_dim)
+    plane = Dy * Dz
+    n_planes = max(1, min(8, Dx, int(0.8 * max_bytes) // (20 * plane)))
+    xs = [(2 * i + 1) * Dx // (2 * n_planes) for i in range(n_planes)]
+    n_hist = max(1, min(plane, int(0.2 * max_bytes) // (4 * 32 * n_planes)))
+    rng = np.random.default_rng(seed)
+    picks = [np.sort(rng.choice(plane, n_hist, replace=False)) for _ in xs]
+    hist = vol.params.flags & L.F_SEMANTIC
+    arrs = {"sdf": [], "wt": [], "color": [], "hist": []}
+    for x, pick in zip(xs, picks):
+        got = vol.download_slab(x, x + 1, hist=bool(hist))
+        arrs["sdf"].append(got["sdf"].astype(np.float32))
+        arrs["wt"].append(got["wt"].astype(np.float32))
+        arrs["color"].append(got["color"].reshape(plane, 3).astype(np.float32))
+        if hist:
+            arrs["hist"].append(got["hist"].reshape(plane, 32)[pick].astype(np.float32))
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, parts in arrs.items():
+        if parts:
+            a = np.stack(parts)
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+            total += a.nbytes
+    assert total <= 64_000_000, total
+    return {"dir": out_dir, "bytes": total, "x_planes": xs, "hist_voxels_per_plane": n_hist if hist else 0,
+            "seed": seed, "arrays": [k for k, v in arrs.items() if v]}
+
+
+def timed_integrate(vol, step, K, warmup, pg=None, device=0, finish=None, instrument=True, after_timed=None):
     """Wall time of K steps (barrier + sync on both sides; `finish`, if given, runs once
-    after them inside the timed region), then the same K steps again with kernel events
-    (integrate kernel, prepass) and once more counting voxels."""
+    after them inside the timed region); `after_timed`, if given, runs right after the clock
+    stops.  With `instrument` the same K steps run again with kernel events (integrate kernel,
+    prepass) and once more counting voxels; without it both records are None."""
     for k in range(warmup):
         step(k)
     if finish is not None:
@@ -303,6 +345,10 @@ def timed_integrate(vol, step, K, warmup, pg=None, device=0, finish=None):
     vol.sync()
     barrier(pg, device)
     elapsed = time.perf_counter() - t0
+    if after_timed is not None:
+        after_timed()
+    if not instrument:
+        return elapsed, None, None
     vol.reset_timing()
     vol.set_instrumentation(events=True, count=False)
     for k in range(K):
@@ -917,9 +963,18 @@ def main():
     ap.add_argument("--frames", type=int, default=16, help="distinct synthetic frames cycled through")
     ap.add_argument("--c4-chunk", type=int, default=47,
                     help="Z-slab chunk of the C4 shards (planes; chunk + halo = three 16-plane units)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pipeline", action="store_true", help="skip pipeline, orbit, C2 and C4-single")
-    ap.add_argument("--no-c4", action="store_true", help="skip the 1024^3 single-GPU C4 measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: beside the headline figure also the kernel-event and voxel-count passes of the "
+                         "timed steps (roofline), the CPU baselines, the C3 pipeline, orbit, mask producer, C2 and "
+                         "C4 records and the HBM copy bandwidth; without it the run sets up, warms up, times "
+                         "--steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps write the volume state the last timed step left (a fixed "
+                         "sample: whole x-planes of sdf, weight and colour, a seeded choice of their voxels' "
+                         "histograms) as DIR/<name>.npy, float32, under 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-pipeline", action="store_true", help="--full: skip pipeline, orbit, C2 and C4-single")
+    ap.add_argument("--no-c4", action="store_true", help="--full: skip the 1024^3 single-GPU C4 measurement")
     ap.add_argument("--no-cull", action="store_true", help="debug: disable unit culling")
     ap.add_argument("--async-prepass", action="store_true", default=True,
                     help="C3 step: frame k's prepass (depth pyramid + unit cull) on the volume's prep stream beside "
@@ -937,8 +992,12 @@ def main():
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="per-launch HBM bytes of the integrate kernel from rocprofv3 PMC (tools/traffic.py)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank, world, local, pg = dist_setup(args.gpus)
+    if args.dump_outputs and (world > 1 or args.only):
+        ap.error("--dump-outputs writes the state of the N = 1 headline run (no --only, one process)")
     # probe: one rank's shard of an N-way C4 volume in a single process (per-rank integrate
     # cost, measurable on one GPU); not a scaling result
     emu_world = int(os.environ.get("BENCH_EMULATE_WORLD", "0"))
@@ -1036,7 +1095,7 @@ def main():
     # CPU baseline first: the forked N-core workers then start from a process that has not
     # touched the GPU yet.
     cpu = cpu_n = None
-    if emu_world <= 1 and not args.no_cpu_baseline:
+    if args.full and emu_world <= 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(frames, p, f0, args.cpu_planes, args.cpu_slabs, 1)
         nw = args.cpu_workers or host_cores()
         if nw > 1:
@@ -1058,15 +1117,53 @@ def main():
         else:
             vol.integrate_dev(dbuf.ptr + i * NPX * 2, rbuf.ptr + i * NPX * 3, mbuf.ptr + i * NPX, Es[i])
 
-    elapsed, tm, tc = timed_integrate(vol, step, args.steps, args.warmup)
+    dumped = {}
+    elapsed, tm, tc = timed_integrate(
+        vol, step, args.steps, args.warmup, instrument=args.full,
+        after_timed=(lambda: dumped.update(dump_outputs(vol, args.dump_outputs))) if args.dump_outputs else None)
+    voxels = int(p.dim[0]) * int(p.dim[1]) * int(p.dim[2]) if emu_world <= 1 else (1024 ** 3) // emu_world
+    value = voxels * args.steps / elapsed / 1e6
+    rec = {
+        "metric": METRIC,
+        "value": round(value, 2),
+        "unit": "Mvoxel-updates/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": "C3: 512^3 semantic TSDF integrate (sdf f32, weight i32, colour u8x3, 32-bin u32 instance "
+                        "histogram), synthetic 640x480 depth+RGB+mask stream (seed 1, noise on), frames resident in "
+                        "HBM" if emu_world <= 1 else
+                        f"probe: shard {emu_rank} of the {emu_world}-way C4 volume (integrate only)",
+            "volume": list(p.dim),
+            "frames_cycled": len(frames),
+        },
+        "full": bool(args.full),
+        "frames_per_s": None,  # the C3 pipeline's rate: --full
+        "integrate_frames_per_s": round(args.steps / elapsed, 2),
+        "prepass": ("frame k's depth pyramid + unit cull on the volume's prep stream beside frame k-1's integrate "
+                    "(semtsdf_integrate_dev_async)") if args.async_prepass else "in front of the frame's integrate",
+    }
+    if dumped:
+        rec["dump_outputs"] = dumped
+    if not args.full:  # the headline figure alone
+        vol.close()
+        for b in (dbuf, rbuf, mbuf):
+            b.free()
+        print(json.dumps(rec), flush=True)
+        return
     kern_ms = tm.integrate_ms / max(tm.n_integrate, 1)
     prep_ms = tm.prep_ms / max(tm.n_prep, 1)
     touched = tc.touched / args.steps
     gated = tc.gated / args.steps
     bytes_per_launch = 16.0 * touched + 14.0 * gated + 6.0 * NPX
     achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9
-    voxels = int(p.dim[0]) * int(p.dim[1]) * int(p.dim[2]) if emu_world <= 1 else (1024 ** 3) // emu_world
-    value = voxels * args.steps / elapsed / 1e6
     traffic, traffic_src = read_traffic(args.traffic_json, D, 1)
     live_units = tc.bricks / args.steps
     free_units = tc.free_units / args.steps
@@ -1089,31 +1186,8 @@ def main():
             c4 = run_c4_single(semtsdf, L, local, frames, f0, args.steps, args.warmup, args.async_prepass)
     copy_bw = copy_bandwidth(local) if not args.no_pipeline else None
 
-    rec = {
-        "metric": METRIC,
-        "value": round(value, 2),
-        "unit": "Mvoxel-updates/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": "C3: 512^3 semantic TSDF integrate (sdf f32, weight i32, colour u8x3, 32-bin u32 instance "
-                        "histogram), synthetic 640x480 depth+RGB+mask stream (seed 1, noise on), frames resident in "
-                        "HBM" if emu_world <= 1 else
-                        f"probe: shard {emu_rank} of the {emu_world}-way C4 volume (integrate only)",
-            "volume": list(p.dim),
-            "frames_cycled": len(frames),
-        },
+    rec.update({
         "frames_per_s": pipeline["frames_per_s"] if pipeline else None,
-        "integrate_frames_per_s": round(args.steps / elapsed, 2),
-        "prepass": ("frame k's depth pyramid + unit cull on the volume's prep stream beside frame k-1's integrate "
-                    "(semtsdf_integrate_dev_async)") if args.async_prepass else "in front of the frame's integrate",
         "integrate_kernel_ms": round(kern_ms, 4),
         "prep_ms": round(prep_ms, 4),
         "prep_exposed_ms": round(elapsed * 1e3 / args.steps - kern_ms, 4),
@@ -1147,7 +1221,7 @@ def main():
         "mask_producer": masks,
         "c2": c2,
         "c4_single_gpu": c4,
-    }
+    })
     print(json.dumps(rec), flush=True)
 
 

@@ -13,7 +13,7 @@ if [ -x $R/tools/membench_units ]; then
   step membench $?
 fi
 cd $R
-timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-pipeline --steps 40 > $O/bench_c3.json 2> $O/bench_c3.err
+timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-pipeline --steps 40 > $O/bench_c3.json 2> $O/bench_c3.err
 step bench $?
 BENCH_ARGS="--no-cpu-baseline --no-pipeline --steps 10 --warmup 2 --frames 4" bash $R/tools/pmc_integrate.sh gpurun_out/$TAG/pmc \
   "SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_WAIT_INST_ANY SQ_INST_CYCLES_SALU" \

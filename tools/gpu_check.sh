@@ -12,6 +12,6 @@ timeout -k 10 400 python3 -u -m pytest tests -m gpu -x -v --timeout 120 --timeou
 step pytest $?
 timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 step smoke $?
-timeout -k 10 300 python3 bench.py "$@" > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 python3 bench.py --full "$@" > $O/bench.json 2> $O/bench.err
 step bench $?
 cat $O/bench.json

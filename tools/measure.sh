@@ -16,10 +16,10 @@ step pmc $?
 python3 $R/tools/traffic.py $O/pmc "$KER" $O/traffic.json 512 > $O/traffic.log 2>&1
 step traffic $?
 cd $R
-timeout -k 10 600 python3 bench.py --traffic-json $O/traffic.json > $O/bench.json 2> $O/bench.err
+timeout -k 10 600 python3 bench.py --full --traffic-json $O/traffic.json > $O/bench.json 2> $O/bench.err
 step bench $?
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 $R/bench.py --no-cpu-baseline --traffic-json $O/traffic.json > $O/bench_prof.json 2> $O/bench_prof.err
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 $R/bench.py --full --no-cpu-baseline --traffic-json $O/traffic.json > $O/bench_prof.json 2> $O/bench_prof.err
 step rocprof_stats $?
 cd $R
 BENCH_DIST_BACKEND=gloo timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_n2.json 2> $O/bench_n2.err

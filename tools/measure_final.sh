@@ -19,7 +19,7 @@ step trace_pipe $?
 python3 $R/tools/timeline.py $O/trace_pipe/trace 40 3 k_march_fused > $O/timeline_pipe.txt 2>&1
 step timeline_pipe $?
 cd /tmp && export TMPDIR=/tmp
-BENCH_EMULATE_WORLD=8 BENCH_EMULATE_RANK=1 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace_c4r1 -o run -- python3 $R/bench.py --no-pipeline --no-cpu-baseline --steps 20 --c4-chunk 47 > $O/c4r1.json 2> $O/c4r1.err
+BENCH_EMULATE_WORLD=8 BENCH_EMULATE_RANK=1 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace_c4r1 -o run -- python3 $R/bench.py --full --no-pipeline --no-cpu-baseline --steps 20 --c4-chunk 47 > $O/c4r1.json 2> $O/c4r1.err
 step trace_c4r1 $?
 python3 $R/tools/timeline.py $O/trace_c4r1 12 3 k_depth_pyramid > $O/timeline_c4r1.txt 2>&1
 step timeline_c4r1 $?

@@ -25,10 +25,10 @@ step pmc_summary $?
 bash $R/tools/diag_c2.sh $TAG/c2 > $O/c2.log 2>&1
 step c2 $?
 cd $R
-timeout -k 10 600 python3 bench.py --traffic-json $O/traffic.json --c2-traffic-json $O/c2/traffic.json > $O/bench.json 2> $O/bench.err
+timeout -k 10 600 python3 bench.py --full --traffic-json $O/traffic.json --c2-traffic-json $O/c2/traffic.json > $O/bench.json 2> $O/bench.err
 step bench $?
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 $R/bench.py --no-cpu-baseline --no-pipeline --traffic-json $O/traffic.json > $O/bench_prof.json 2> $O/bench_prof.err
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 $R/bench.py --full --no-cpu-baseline --no-pipeline --traffic-json $O/traffic.json > $O/bench_prof.json 2> $O/bench_prof.err
 step rocprof_stats $?
 cd $R
 bash $R/tools/pmc_march.sh gpurun_out/$TAG/pmcm > $O/pmcm_summary.txt 2>&1
