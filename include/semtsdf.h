@@ -132,8 +132,8 @@ typedef struct semtsdf_timing {
     uint64_t n_prep;
     uint64_t free_units;  /* of those, units whose touched voxels all have f == 1 (count mode only) */
     uint64_t full_units;  /* of those, free units whose every voxel is touched (no projection; count mode only) */
-    uint64_t lazy_voxels; /* touched voxels of steady lines whose +1 weight went to the line's pending count
-                             instead of a weight store (count mode only) */
+    uint64_t lazy_voxels; /* always 0: counted the lazy-weight experiment's voxels (removed);
+                             the field stays for the ABI */
     uint64_t assoc_exact_frames; /* association decisions that took the exact f32 path (always counted) */
     uint64_t assoc_exact_rows;   /* rows decided on it, summed over those decisions */
     uint64_t touched_lines;      /* 128-B lines of the sdf array (8 y x 4 z voxels of a tile) holding a

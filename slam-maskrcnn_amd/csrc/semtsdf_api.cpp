@@ -267,11 +267,7 @@ int local_planes(const semtsdf_params* p, int* chunk, int* halo) {
     // round may lack this shard's position
     const int n = p->z_nshards;
     for (int r = 0; r * n < nchunks; ++r)
-#ifdef SEMTSDF_DEAL_RR
-        if (r * n + p->z_shard < nchunks) ++mine;
-#else
         if (r * n + ((r & 1) ? n - 1 - p->z_shard : p->z_shard) < nchunks) ++mine;
-#endif
     return mine * (p->z_chunk + 1);
 }
 
@@ -1052,7 +1048,6 @@ int semtsdf_create(const semtsdf_params* p, int device, semtsdf_vol** out) {
         if ((rc = dev_alloc(v, (void**)&pyr.l0, (size_t)pyr.w1 * 4 * pyr.h1 * 4 * sizeof(uint2)))) return bail(rc);
         if ((rc = dev_alloc(v, (void**)&pyr.l1, (size_t)pyr.w1 * pyr.h1 * sizeof(uint2)))) return bail(rc);
         if ((rc = dev_alloc(v, (void**)&f.unit_list, unit_list_capacity(g) * sizeof(unsigned)))) return bail(rc);
-        // + the integrate's dynamic counters (per XCD and workgroup slot), kListCountStride words apart
         if ((rc = dev_alloc(v, (void**)&f.list_count, kListCountWords * sizeof(unsigned)))) return bail(rc);
         // every unit in at most one list, + one pad per list, bases rounded up to even; at least two
         // entries per persistent wave (k_integrate reads a wave's first free group unconditionally)
@@ -1930,7 +1925,6 @@ int semtsdf_download_slab(semtsdf_vol* v, int x0, int x1, float* sdf, int32_t* w
     const uint64_t vb = (uint64_t)x0 * plane, ve = (uint64_t)x1 * plane;
     int rc;
     if (sdf && (rc = vox_xfer(v, sdf, v->b.sdf, true, "sdf", s, vb, ve))) return rc;
-    if (wt) HIPC(launch_flush_lazy(v->g, v->b, s));  // pending increments of steady lines into the weights
     if (wt && (rc = vox_xfer(v, wt, v->b.wt, true, "weight", s, vb, ve))) return rc;
     if (color) {
         rc = color_xfer(v, color, true, s, vb, ve);
@@ -1982,9 +1976,6 @@ int semtsdf_upload(semtsdf_vol* v, const float* sdf, const int32_t* wt, const vo
     // derived maps first: a transfer that fails half-way must not leave steady flags or an
     // empty-space map that describe the old contents (0 = unknown is always safe)
     v->bmin_stale = true;
-    // the weights a flag byte's pending increments apply to stay: fold them in before the
-    // flags are dropped (an upload of the weights replaces them, pending counts included)
-    if (sdf && !wt) HIPC(launch_flush_lazy(v->g, v->b, s));
     if (sdf || wt) HIPC(hipMemsetAsync(v->b.sflag, 0, v->g.nvox / 32 + 1, s));  // steady flags: unknown
     if (sdf && (rc = vox_xfer(v, const_cast<float*>(sdf), v->b.sdf, false, "sdf", s, 0, nref(v)))) return rc;
     if (wt && (rc = vox_xfer(v, const_cast<int32_t*>(wt), v->b.wt, false, "weight", s, 0, nref(v)))) return rc;
@@ -2062,7 +2053,6 @@ int semtsdf_export_surface(semtsdf_vol* v, float sdf_max, int32_t min_weight, se
     HIPC(hipSetDevice(v->device));
     hipStream_t s = v->stream;
     if (int rc = after_bmin(v, s)) return rc;
-    HIPC(launch_flush_lazy(v->g, v->b, s));  // pending weight increments (lazy-weight builds)
     unsigned long long* cnt_d = nullptr;
     HIPC(hipMalloc((void**)&cnt_d, sizeof(unsigned long long)));
     SurfacePoint* pts_d = nullptr;
@@ -2141,7 +2131,7 @@ int semtsdf_get_timing(semtsdf_vol* v, semtsdf_timing* out) {
     out->bricks = c[3];
     out->free_units = c[4];
     out->full_units = c[5];
-    out->lazy_voxels = c[6];
+    out->lazy_voxels = 0;  // counter 6 is unused (semtsdf.h)
     out->touched_lines = c[7];
     unsigned xr[3] = {0, 0, 0};  // AssocExact::frames, rows, pos_max
     HIPC(hipMemcpy(xr, &v->exact_d->frames, sizeof(xr), hipMemcpyDeviceToHost));

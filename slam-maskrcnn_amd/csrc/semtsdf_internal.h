@@ -17,16 +17,12 @@ constexpr int kZAlign = 32;      // stored z planes per x,y column: a multiple o
 constexpr int kBrickDistCap = SEMTSDF_BRICK_DIST_CAP;  // brick distance map: radius of the largest skip box (bricks)
 constexpr int kListSegs = 64;    // segments (and counters) of the live-unit list
 constexpr unsigned kPreWaves = 65534;  // k_integrate reads entries 2w+1 (+4) ahead for waves w < kPreWaves
+constexpr unsigned kFirstTabSlots = kListSegs * 256;  // wave slots of the first-group table k_compact_lists writes
 constexpr int kListCountStride = 64;  // counters 256 B apart (separate memory channels)
-#ifndef SEMTSDF_DYN_SUB
-#define SEMTSDF_DYN_SUB 8
-#endif
-constexpr unsigned kDynSub = SEMTSDF_DYN_SUB;           // integrate dynamic counters per XCD (power of two)
-constexpr int kDynCounters = 8 * SEMTSDF_DYN_SUB;       // after the list counts (zeroed by the prepass)
-// words of list_count: the segment counts, the dynamic counters, then the compact lists' (base, total)
-constexpr int kListTotalsWord = (3 * kListSegs + kDynCounters) * kListCountStride;
-constexpr int kListCountWords = kListTotalsWord + 8;
 constexpr int kLists = 3;             // live-unit lists: general, free (projected), full free (no projection)
+// words of list_count: the segment counts of the lists, then the compact lists' (base, total)
+constexpr int kListTotalsWord = kLists * kListSegs * kListCountStride;
+constexpr int kListCountWords = kListTotalsWord + 8;
 
 // Geometry of the locally stored part of the volume.
 struct VolGeom {
@@ -86,8 +82,7 @@ struct VolBufs {
                        // a voxel of brick 4q + j crossed the skip threshold since the last map update
     uint32_t* dlist;   // [1 + quads]: count, then the quads whose dirty word is nonzero
     uint8_t* sflag;    // per 128-B sdf line (32 voxels): s >= 1 = every sdf is 1.0f and every weight
-                       // < 2^23 (k_integrate skips the sdf traffic of such lines), and s - 1 increments
-                       // of every weight of the line are pending (lazy weights); 0 = unknown
+                       // < 2^23 (k_integrate skips the sdf traffic of such lines); 0 = unknown
 };
 
 // Per-frame images of the integrate: depth in metres and rgb+label per pixel (row-major,
@@ -152,10 +147,9 @@ struct IntegrateArgs {
     float rmu;                     // RN(1/mu), for the exact division by mu (k_integrate)
     int fastdiv;                   // mu in [2^-20, 2^20]: divisions by mu/(w+1) via RN reciprocals
     unsigned* unit_list;           // live units: three lists (general, free, full free) of kListSegs segments (k_cull_units)
-    unsigned* list_count;          // [3][kListSegs * kListCountStride] entries per segment, then the dynamic
-                                   // counters, then the compact lists' (base, total) pairs (k_compact_lists)
+    unsigned* list_count;          // [kLists][kListSegs * kListCountStride] entries per segment (zeroed by the frame
+                                   // prepass), then the compact lists' (base, total) pairs (k_compact_lists)
     unsigned* units;               // the three lists back to back (k_compact_lists), each followed by a ~0u pad
-                                   // counters of the 8 XCDs (all zeroed by the frame prepass)
     int free_ok;                   // free units allowed: gated colour with gate <= 1 (f == 1 updates sdf/weight only)
     int color_wide;                // colour stored as int32 x 4 (else u8 x 4; see semtsdf_vol::color_wide)
     unsigned long long* wtrace;    // instrumentation (build with SEMTSDF_WAVE_TRACE=1, run with
@@ -335,7 +329,6 @@ size_t mask_scratch_kept_offset();
 // passes (k_brick_oct_lds); both give the same maps.
 hipError_t launch_brick_min(const VolGeom& g, const VolBufs& b, bool all, hipStream_t s, bool global_passes = false);
 hipError_t launch_fill_volume(const VolGeom& g, const VolBufs& b, uint32_t flags, hipStream_t s);
-hipError_t launch_flush_lazy(const VolGeom& g, const VolBufs& b, hipStream_t s);  // lazy weights -> weights
 hipError_t launch_depth_pyramid(const uint16_t* depth, const uint8_t* rgb, uint8_t* mask, int w, int h,
                                 float scale, const DepthPyramid& p, unsigned* list_count, hipStream_t s,
                                 const uint8_t* lut = nullptr);  // lut: relabel the mask in place (k_relabel folded in)

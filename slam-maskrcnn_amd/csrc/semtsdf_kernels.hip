@@ -29,10 +29,6 @@
 #include "semtsdf_internal.h"
 #include "semtsdf_libm.h"
 
-#ifndef SEMTSDF_LAZY_WEIGHT
-#define SEMTSDF_LAZY_WEIGHT 0  // lazy weights (k_integrate): measured slower, off by default
-#endif
-
 namespace semtsdf {
 
 // ------------------------------------------------------------------------------------
@@ -97,12 +93,7 @@ __device__ __forceinline__ float vox_coord(float p, float start, float voxel, fl
 // a work density that drifts along z evens out over pairs of rounds.  Local chunk r of a
 // shard is its chunk of round r (only the last round may lack it).
 __host__ __device__ __forceinline__ int chunk_pos(int round, int shard, int n) {
-#ifdef SEMTSDF_DEAL_RR
-    (void)round; (void)n;
-    return shard;
-#else
     return (round & 1) ? n - 1 - shard : shard;
-#endif
 }
 __host__ __device__ __forceinline__ int chunk_owner(int c, int n) {
     const int r = c / n;
@@ -276,13 +267,6 @@ __global__ __launch_bounds__(256) void k_brick_plain(VolGeom g, const float* __r
 }
 
 __device__ __forceinline__ float skip_threshold(const VolGeom& g);
-
-#ifndef SEMTSDF_BRICK_DIST
-#define SEMTSDF_BRICK_DIST 1
-#endif
-#ifndef SEMTSDF_BRICK_OCT
-#define SEMTSDF_BRICK_OCT 1  // unsharded marches use the octant boxes of their direction
-#endif
 
 __global__ __launch_bounds__(256) void k_brick_dilate(VolGeom g, const float* __restrict__ plain, float* __restrict__ bmin,
                                                       uint64_t* __restrict__ d0, uint32_t* __restrict__ dlist) {
@@ -516,7 +500,7 @@ hipError_t launch_brick_min(const VolGeom& g, const VolBufs& b, bool all, hipStr
     const unsigned nw = all ? nq : (nq < 4096u ? nq : 4096u);  // waves (list mode: grid-strided)
     hipLaunchKernelGGL(k_brick_plain, dim3((nw + 3) / 4), dim3(256), 0, s, g, b.sdf, b.bplain, b.bdirty, b.dlist,
                        all ? 1 : 0);
-    const bool dist = SEMTSDF_BRICK_DIST && b.bdist && b.boct && b.botmp;
+    const bool dist = b.bdist && b.boct && b.botmp;
     const int Lx = oct_lds_lines(g.nbx), Ly = oct_lds_lines(g.nby), Lz = oct_lds_lines(g.nbz);
     if (dist && !global_passes && Lx && Ly && Lz) {  // plain -> x -> boct -> y -> botmp -> z -> boct (+ bdist)
         const unsigned lx = (unsigned)g.nby * g.nbz, ly = (unsigned)g.nbx * g.nbz, lz = (unsigned)g.nbx * g.nby;
@@ -538,28 +522,6 @@ hipError_t launch_brick_min(const VolGeom& g, const VolBufs& b, bool all, hipStr
         const unsigned ns = (unsigned)g.nsx * g.nsy * g.nsz;
         if (b.sbmin && ns) hipLaunchKernelGGL(k_brick_super, dim3((ns + 3) / 4), dim3(256), 0, s, g, b.bmin, b.sbmin);
     }
-    return hipGetLastError();
-}
-
-// Folds the pending weight increments of steady lines into the weights (k_integrate's lazy
-// weights): one lane per voxel, the 32 voxels of a line in one half-wave, which reads the flag
-// byte before its first lane resets it (loads of one wave-instruction precede its stores).
-__global__ __launch_bounds__(256) void k_flush_lazy(int32_t* __restrict__ wt, uint8_t* __restrict__ sflag, uint64_t nvox) {
-    for (uint64_t v = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; v < nvox; v += (uint64_t)gridDim.x * blockDim.x) {
-        const unsigned f = sflag[v >> 5];
-        if (f > 1u) {
-            wt[v] += (int)f - 1;
-            if ((v & 31u) == 0u) sflag[v >> 5] = 1u;
-        }
-    }
-}
-
-hipError_t launch_flush_lazy(const VolGeom& g, const VolBufs& b, hipStream_t s) {
-    if (!SEMTSDF_LAZY_WEIGHT) return hipSuccess;  // no pending counts exist in this build
-    const uint64_t n = g.nvox;
-    if (n == 0) return hipSuccess;  // a shard that owns no chunk
-    const unsigned grid = (unsigned)((n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536);
-    hipLaunchKernelGGL(k_flush_lazy, dim3(grid), dim3(256), 0, s, b.wt, b.sflag, n);
     return hipGetLastError();
 }
 
@@ -595,8 +557,6 @@ __device__ __forceinline__ void pyramid_tile(const uint16_t* __restrict__ depth,
     auto relab = [&](unsigned m) { return (s_lut[m >> 2] >> (8 * (m & 3))) & 0xFFu; };
     if (list_count && tx == 0 && ty == 0 && t < kLists * kListSegs)  // this frame's lists (general, free, full)
         list_count[(t & (kListSegs - 1)) * kListCountStride + (t >> 6) * kListSegs * kListCountStride] = 0u;
-    if (list_count && tx == 0 && ty == 0 && t < kDynCounters)  // the integrate's dynamic counters
-        list_count[(kLists * kListSegs + t) * kListCountStride] = 0u;
     const int r = t >> 3;          // row in tile
     const int c4 = (t & 7) * 4;    // first column in tile
     const int yy = ty * 32 + r;
@@ -718,12 +678,7 @@ hipError_t launch_depth_pyramid(const uint16_t* depth, const uint8_t* rgb, uint8
 // fewer voxels than whole tiles (the cull is near exact at unit resolution: 23.5 M against
 // 28.0 M visited voxels per 512^3 frame) and measured 14 % faster; quarter tiles visit 5 %
 // fewer again but the cull of 4x as many units costs more than that saves.
-#ifndef SEMTSDF_UNIT_X
-#define SEMTSDF_UNIT_X 1
-#define SEMTSDF_UNIT_Y 8
-#define SEMTSDF_UNIT_Z 16
-#endif
-constexpr int UX = SEMTSDF_UNIT_X, UY = SEMTSDF_UNIT_Y, UZ = SEMTSDF_UNIT_Z;
+constexpr int UX = 1, UY = 8, UZ = 16;
 // Timing probes of the integrate (SEMTSDF_DEBUG_INTEGRATE=n at run time) exist only in a
 // build with -DSEMTSDF_INTEGRATE_PROBES=1: the production kernel carries no probe branches.
 #ifndef SEMTSDF_INTEGRATE_PROBES
@@ -986,15 +941,9 @@ hipError_t launch_cull(const IntegrateArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-#ifndef SEMTSDF_TAIL_CULL_PROBE
-#define SEMTSDF_TAIL_CULL_PROBE 0  // instrumentation build: a whole-grid unit cull in the integrate's tail
-#endif
-#ifndef SEMTSDF_XCD_SPLIT
-#define SEMTSDF_XCD_SPLIT 1  // each XCD's waves take a contiguous eighth of every list (list_view)
-#endif
 // The cull's segments compacted into one array: list l at an even base (so a group's two entries are
 // one 8-byte scalar load), followed by a ~0u pad (the second entry of a list's last group when
-// its count is odd), bases and totals after the dynamic counters of list_count.  One wave per
+// its count is odd), bases and totals after the segment counts of list_count.  One wave per
 // (segment, list): lane j holds the count of segment j of every list; the wave's segment offset
 // is the exclusive prefix of its list's counts.  Runs on the prep stream after the cull, so the
 // integrate reads its first group's entries without the counts' prefix (one dependent load less
@@ -1045,11 +994,13 @@ __global__ __launch_bounds__(256) void k_compact_lists(unsigned* __restrict__ li
         for (int k = 0; k < 4; ++k)
             if (i0 + 256u * k < n) dst[i0 + 256u * k] = e[k];
     }
-    if (SEMTSDF_XCD_SPLIT && l == first_list && nwaves) {
+    if (l == first_list && nwaves) {
         // the first-group table of the XCD split (k_integrate, list_view): wave slot w (workgroup w / 4,
         // XCD xi = workgroup % 8, index wx among the XCD's waves) starts at group lo(xi) + wx of the list;
         // its two entries are read here from the cull's segments (the compacted array is being written
-        // by the other workgroups), the segment found by a binary search over the inclusive prefix
+        // by the other workgroups), the segment found by a binary search over the inclusive prefix.
+        // The grid's kListSegs workgroups of this list cover slots w < kFirstTabSlots
+        // (integrate_pre_waves offers no larger grid).
         if (threadIdx.x < 64u) s_incl[threadIdx.x] = incl;
         __syncthreads();
         const unsigned w = seg * 256u + threadIdx.x;
@@ -1152,25 +1103,9 @@ __device__ __forceinline__ uint64_t unit_tile(const VolGeom& g, const UnitPos& u
     return tile_xterm(g, up.x) + __umul24((uint32_t)up.uy, g.ty) + (z0 >> 5) * 256u + ((z0 >> 2) & 7u) * 32u;
 }
 
-#ifndef SEMTSDF_STEADY
-#define SEMTSDF_STEADY 1  // skip the sdf traffic of steady lines (Ld::skip)
-#endif
-
-// Lazy weights of steady lines.  A steady line (every sdf exactly 1.0f) whose 32 voxels are
-// all touched with f == 1 changes only its weights, each by +1, when the colour/histogram
-// gate rejects f == 1 (free_ok modes): the increment is kept as a per-line pending count in
-// the line's flag byte instead of a read-modify-write of the 128-B weight line (and the sdf
-// line is skipped as a steady line anyway).  Flag byte s: 0 = not steady; s >= 1 = steady with
-// s - 1 pending increments of every weight of the line.  Any other update of the line adds
-// the pending count first (stage_compute), and k_flush_lazy folds the counts into the weights
-// before they are read out (download, upload, checkpoint).
-#ifndef SEMTSDF_CHAIN
-#define SEMTSDF_CHAIN 1  // a wave's last unit of a list overlaps the first unit of its next list
-#endif
 #ifndef SEMTSDF_WAVE_TRACE
 #define SEMTSDF_WAVE_TRACE 0  // instrumentation build only: per-wave phase timestamps (IntegrateArgs::wtrace)
 #endif
-constexpr unsigned kFlagMax = 255u;  // s - 1 <= 254 pending increments
 
 struct Proj {
     float qz[4];
@@ -1208,7 +1143,6 @@ __device__ __forceinline__ StoreMeta store_meta(const Cls& C) {
 
 struct Ld {
     bool skip;  // steady line: s4 not loaded, every value is 1.0f
-    bool lazy;  // steady line, all 32 voxels touched with f == 1: only the flag byte changes
     float4 s4;
     int4 w4;
     uint4 c8;
@@ -1222,7 +1156,6 @@ struct Out {
     float4 s4;
     int4 w4;
     bool skip;       // the line's sdf was neither loaded nor changes (steady line)
-    bool lazy;       // the line's weights take one more pending increment (flag byte + 1)
     unsigned oflag;  // the line's steady flag before this update
     bool cross;      // a voxel's sdf crossed the skip threshold (its brick's map entry may flip)
     uint32_t ub;     // Proj::ub of the unit
@@ -1239,9 +1172,7 @@ __device__ __forceinline__ void stage_project(const IntegrateArgs& a, const Unit
     const VolGeom& g = a.g;
     P.ub = (uint32_t)unit_tile(g, up);
     if (FULL) {  // full free unit (unit_cull == 3): every voxel touched with f == 1, nothing to project
-        P.sflag = SEMTSDF_STEADY ? (unsigned)a.b.sflag[(P.ub + (unsigned)lane_zq(lane) * 32u +
-                                                        (unsigned)lane_y(lane) * 4u) >> 5]
-                                 : 0u;
+        P.sflag = (unsigned)a.b.sflag[(P.ub + (unsigned)lane_zq(lane) * 32u + (unsigned)lane_y(lane) * 4u) >> 5];
 #pragma unroll
         for (int k = 0; k < 4; ++k) P.rec[k] = make_uint2(1u, 0u);  // "depth != 0"
         P.vmask = up.ok ? 0xFu : 0u;  // every voxel of a real unit
@@ -1341,9 +1272,7 @@ __device__ __forceinline__ void stage_project(const IntegrateArgs& a, const Unit
                                 : npx;
     }
     // steady flag of the lane's sdf line (one byte per 128-B line, unconditional)
-    P.sflag = SEMTSDF_STEADY ? (unsigned)a.b.sflag[(P.ub + (unsigned)lane_zq(lane) * 32u +
-                                                    (unsigned)lane_y(lane) * 4u) >> 5]
-                             : 0u;
+    P.sflag = (unsigned)a.b.sflag[(P.ub + (unsigned)lane_zq(lane) * 32u + (unsigned)lane_y(lane) * 4u) >> 5];
     // unconditional gathers (an off-image voxel reads a zero record: depth 0); a free unit needs
     // only the depth word (touched <=> depth != 0, f == 1)
 #pragma unroll
@@ -1354,12 +1283,6 @@ __device__ __forceinline__ void stage_project(const IntegrateArgs& a, const Unit
                 0u);
         else
             P.rec[k] = a.pyr.px[(kProbes && a.debug == 21) ? 0u : (unsigned)P.img[k]];  // 21: probe, one address
-#if SEMTSDF_PROBE_GATHER2
-        {  // timing probe: a second gather per voxel (no effect on results)
-            const uint2 extra = a.pyr.px[(unsigned)P.img[k] ^ 1u];
-            P.rec[k].y += (extra.x == 0x7fc00001u) ? 1u : 0u;
-        }
-#endif
     }
 }
 
@@ -1473,19 +1396,16 @@ __device__ __forceinline__ void stage_classify(const IntegrateArgs& a, const Pro
     }
 }
 
-#ifndef SEMTSDF_FULLROW
-#define SEMTSDF_FULLROW 0
-#endif
-// State traffic per lane (SEMTSDF_FULLROW 0): a lane loads and stores its 16-B vectors only
+// State traffic per lane: a lane loads and stores its 16-B vectors only
 // when it updates (sdf/weight: a touched voxel; colour: a gated one); a 128-B line of a
 // per-voxel array is the 8 lanes of one z-quad (lane % 8).  The line's steady flag is then
 // decided from the lanes that loaded their values plus what the old flag says of the others:
 // an untouched lane of a steady line still holds sdf 1.0f and a weight < 2^23; of a line not
 // known steady, nothing (it stays 0, "unknown").  (r03's per-lane build decided the flag from
 // every lane's values, the dummy line's included, and flagged unsteady lines steady:
-// profiles/r03/s2/gputest_full_row_0_failure.txt.)  SEMTSDF_FULLROW 1: whole-line traffic
-// (all 8 lanes load and store when any of them updates; every line written back fully dirty).
-static_assert(!SEMTSDF_LAZY_WEIGHT || SEMTSDF_FULLROW, "lazy weights need whole-line state traffic");
+// profiles/r03/s2/gputest_full_row_0_failure.txt.  r03's whole-line traffic, all 8 lanes
+// loading and storing when any of them updates, and the lazy weights built on it were
+// measured slower: DESIGN.md §3, "Whole-line state traffic" and "Tried earlier ... Lazy weights".)
 constexpr uint64_t line_lanes() {  // lanes of one line of slot 0, z-quad 0: zq + LZQ y
     uint64_t m = 0;
     for (int y = 0; y < UY; ++y) m |= 1ull << (LZQ * y);
@@ -1493,108 +1413,63 @@ constexpr uint64_t line_lanes() {  // lanes of one line of slot 0, z-quad 0: zq 
 }
 constexpr uint64_t kLineLanes = line_lanes();
 
-__device__ __forceinline__ bool tile_line_any(bool p) {
-    static_assert(UY == 8 && UX == 1, "lane = zq + LZQ y + kUnitLanes slot");
-    if (!SEMTSDF_FULLROW) return p;
-    const uint64_t b = __ballot(p);
-    const int lane = (int)__lane_id();
-    return ((b >> (lane % LZQ + lane_slot(lane) * kUnitLanes)) & kLineLanes) != 0ull;
-}
-
 // true when p holds on all 8 lanes of the lane's line (inactive lanes count as true)
 __device__ __forceinline__ bool tile_line_all(bool p) {
+    static_assert(UY == 8 && UX == 1, "lane = zq + LZQ y + kUnitLanes slot");
     const uint64_t b = __ballot(!p);
     const int lane = (int)__lane_id();
     return ((b >> (lane % LZQ + lane_slot(lane) * kUnitLanes)) & kLineLanes) == 0ull;
 }
 
-#ifndef SEMTSDF_NT_LOAD
-#define SEMTSDF_NT_LOAD 0  // nt loads measured 3-5 % slower once the pipeline was chained (r03, same box)
-#endif
-#ifndef SEMTSDF_NT_STORE
-#define SEMTSDF_NT_STORE 0  // default-policy state stores: r06 A/B 73.7 -> 72.2 us (C3), 19.1 -> 18.9 us (C2) over six rounds (profiles/r06/ab/r06_store_policy.txt); nt until r05
-#endif
-#ifndef SEMTSDF_NT_HIST
-#define SEMTSDF_NT_HIST 0  // histogram lines are partial (one bin plane per lane): default policy
-#endif
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-// 16-B state accesses (sdf, weight, colour, histogram), optionally non-temporal
-template <class T, bool NT = SEMTSDF_NT_LOAD>
+// 16-B state accesses (sdf, weight, colour, histogram) at the default cache policy
+// (non-temporal loads and stores were measured slower: DESIGN.md §3, "Whole-line state traffic (r03),
+// non-temporal stores")
+template <class T>
 __device__ __forceinline__ T ld_state(const void* p) {
     static_assert(sizeof(T) == 16, "16-byte vectors");
-    if (NT) {
-        const u32x4 r = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-        T t;
-        __builtin_memcpy(&t, &r, 16);
-        return t;
-    }
     return *reinterpret_cast<const T*>(p);
 }
-template <class T, bool NT = SEMTSDF_NT_STORE>
+template <class T>
 __device__ __forceinline__ void st_state(void* p, const T& v) {
     static_assert(sizeof(T) == 16, "16-byte vectors");
-    if (NT) {
-        u32x4 r;
-        __builtin_memcpy(&r, &v, 16);
-        __builtin_nontemporal_store(r, reinterpret_cast<u32x4*>(p));
-        return;
-    }
     *reinterpret_cast<T*>(p) = v;
 }
 
-#ifndef SEMTSDF_DUMMY0
-#define SEMTSDF_DUMMY0 1  // the dummy address of a lane with nothing to load: 1 the array's start, 0 its unit's first line
-#endif
 // Unconditional loads: a lane with nothing to load reads the dummy line (one 16-B vector
-// shared by all such lanes), so the issue count is the same on every path.
+// shared by all such lanes), so the issue count is the same on every path.  The dummy line
+// is the array's first vector (offset 0, selected in 32 bits: one base pointer per array),
+// which stays in L2 like a steady line (the unit's first line instead was an extra line
+// fetched whenever that line itself has no update: DESIGN.md §3, "r06: traffic").
 template <bool SEM, bool CI32, bool VOTE, bool FREE>
 __device__ __forceinline__ void stage_load(const IntegrateArgs& a, const UnitPos& up, unsigned coff, const Cls& C,
                                            Ld& L) {
     const VolGeom& g = a.g;
-    // wave-uniform unit bases (scalar) + the lane's 32-bit element offset; a lane with
-    // nothing to load reads the unit's first vector instead (same line for all of them)
+    // wave-uniform unit base (scalar) + the lane's 32-bit element offset
     (void)up;
     const uint32_t ub = C.ub;
     const uint32_t v = ub + coff;
-    // a lane with nothing to load reads the array's first vector (offset 0): one base pointer
-    // per array, the offset selected in 32 bits
     const uint4* dummy = reinterpret_cast<const uint4*>(a.b.sdf);
-    const bool t = tile_line_any(C.tmask != 0u), gt = tile_line_any(C.gmask != 0u);
-    const unsigned lt = t ? coff : 0u, lg = gt ? coff : 0u;
+    const bool t = C.tmask != 0u, gt = C.gmask != 0u;
+    const unsigned lg = gt ? coff : 0u;
     // Steady line: every sdf of the line is exactly 1.0f with weight < 2^23 (flag) and every
     // touched voxel of it has f == 1.0f, so (1 w + 1) / (w + 1) == 1 exactly (w + 1 < 2^24 in
-    // both the reciprocal and the IEEE path): the line's sdf is neither read nor written.
+    // both the reciprocal and the IEEE path): the lane's sdf is neither read nor written.
     bool fone = true;
 #pragma unroll
     for (int k = 0; k < 4; ++k) fone &= (((C.tmask >> k) & 1u) == 0u) | (C.fv[k] == 1.0f);
-    // (whole-line traffic: the whole line skips together; per-lane: each lane for itself)
-    const bool skip = SEMTSDF_STEADY && (SEMTSDF_FULLROW ? tile_line_all((C.sflag != 0u) & fone) : ((C.sflag != 0u) & fone));
-    // lazy: steady, every voxel of the line touched (f == 1), pending count below the cap
-    const bool lazy = SEMTSDF_STEADY && SEMTSDF_LAZY_WEIGHT && !VOTE && a.free_ok &&
-                      tile_line_all((C.sflag != 0u) & (C.sflag < kFlagMax) & fone & (C.tmask == 15u));
+    const bool skip = (C.sflag != 0u) & fone;  // each lane for itself
     L.skip = skip;
-    L.lazy = lazy;
-    if (SEMTSDF_DUMMY0) {
-        // a lane with nothing to load reads the array's first vector, like a steady line: the line
-        // stays in L2, where the unit's first line (the other choice) is an extra line fetched
-        // whenever that line itself has no update
-        L.s4 = ld_state<float4>(a.b.sdf + ((skip | !t) ? 0u : v));
-        L.w4 = ld_state<int4>(a.b.wt + ((lazy | !t) ? 0u : v));
-    } else {
-        L.s4 = ld_state<float4>(a.b.sdf + (skip ? 0u : ub + lt));
-        L.w4 = ld_state<int4>(a.b.wt + (lazy ? 0u : ub + lt));
-    }
+    L.s4 = ld_state<float4>(a.b.sdf + ((skip | !t) ? 0u : v));
+    L.w4 = ld_state<int4>(a.b.wt + (t ? v : 0u));
     if (FREE) return;  // sdf and weight only
     if (CI32) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) L.c32[k] = reinterpret_cast<const int4*>(a.b.color)[(uint64_t)ub + lg + (gt ? k : 0)];
-    } else if (SEMTSDF_DUMMY0) {
-        L.c8 = ld_state<uint4>(reinterpret_cast<const uint32_t*>(a.b.color) + (gt ? v : 0u));
     } else {
-        L.c8 = ld_state<uint4>(reinterpret_cast<const uint32_t*>(a.b.color) + ub + lg);
+        L.c8 = ld_state<uint4>(reinterpret_cast<const uint32_t*>(a.b.color) + (gt ? v : 0u));
     }
     if (SEM)
-        L.h4 = ld_state<uint4, SEMTSDF_NT_HIST>(a.b.hist + (C.hmode == 1u ? (uint64_t)C.hlab * g.nvox + v : 0ull));
+        L.h4 = ld_state<uint4>(a.b.hist + (C.hmode == 1u ? (uint64_t)C.hlab * g.nvox + v : 0ull));
     if (VOTE) {
         L.vc4 = *(t ? reinterpret_cast<const int4*>(a.b.cls + v) : reinterpret_cast<const int4*>(dummy));
         L.vn4 = *(t ? reinterpret_cast<const int4*>(a.b.cls_cnt + v) : reinterpret_cast<const int4*>(dummy));
@@ -1611,12 +1486,9 @@ __device__ __forceinline__ void stage_compute(const IntegrateArgs& a, const floa
     const float so[4] = {L.skip ? 1.0f : L.s4.x, L.skip ? 1.0f : L.s4.y, L.skip ? 1.0f : L.s4.z,
                          L.skip ? 1.0f : L.s4.w};
     O.skip = L.skip;
-    O.lazy = L.lazy;
     O.oflag = C.sflag;
     O.ub = C.ub;
-    // the stored weights plus the line's pending increments (0 unless the line is steady)
-    const int pend = (SEMTSDF_STEADY && SEMTSDF_LAZY_WEIGHT && C.sflag) ? (int)C.sflag - 1 : 0;
-    const int wo[4] = {L.w4.x + pend, L.w4.y + pend, L.w4.z + pend, L.w4.w + pend};
+    const int wo[4] = {L.w4.x, L.w4.y, L.w4.z, L.w4.w};
     float sn[4];
     int wn[4];
     // the reciprocal path's range over the lane's 4 voxels (touched or not: a running maximum of the
@@ -1743,16 +1615,15 @@ __device__ __forceinline__ void voxel_add(uint32_t* p, uint32_t v) {
     (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-template <bool SEM, bool CI32, bool VOTE, bool FREE, bool COUNT>
+template <bool SEM, bool CI32, bool VOTE, bool FREE>
 __device__ __forceinline__ void stage_store(const IntegrateArgs& a, const UnitPos& up, unsigned coff,
-                                            const StoreMeta& M, const Out& O, unsigned& n_lazy) {
+                                            const StoreMeta& M, const Out& O) {
     const VolGeom& g = a.g;
     const unsigned tmask = M.meta & 15u, gmask = (M.meta >> 4) & 15u, hmode = (M.meta >> 8) & 3u,
                    hlab = M.meta >> 16;
-    const bool trow = tile_line_any(tmask != 0u), grow = tile_line_any(gmask != 0u);
     // the lines with an update stay active together (the flag below is a ballot over a line)
-    const bool line = SEMTSDF_FULLROW ? trow : ((__ballot(tmask != 0u) >> ((int)__lane_id() % LZQ +
-                                                 lane_slot((int)__lane_id()) * kUnitLanes)) & kLineLanes) != 0ull;
+    const bool line = ((__ballot(tmask != 0u) >> ((int)__lane_id() % LZQ + lane_slot((int)__lane_id()) * kUnitLanes)) &
+                       kLineLanes) != 0ull;
     if (!line) return;
     const uint64_t v = O.ub + coff;
     {
@@ -1784,12 +1655,11 @@ __device__ __forceinline__ void stage_store(const IntegrateArgs& a, const UnitPo
             }
         }
     }
-    if (COUNT && O.lazy) n_lazy += 4u;
-    if (!(kProbes && a.debug == 10) && !O.lazy && trow) {  // 10: timing probe, loads but no sdf/weight stores
+    if (!(kProbes && a.debug == 10) && tmask != 0u) {  // 10: timing probe, loads but no sdf/weight stores
         if (!O.skip) st_state(a.b.sdf + v, O.s4);
         st_state(a.b.wt + v, O.w4);
     }
-    if (SEMTSDF_STEADY) {  // the line's flag byte after this update (one lane per line writes)
+    {  // the line's flag byte after this update (one lane per line writes)
         // every sdf exactly 1.0f (bits: AND and OR of the four both equal 1.0f's) and every weight < 2^23
         const unsigned s_and = __float_as_uint(O.s4.x) & __float_as_uint(O.s4.y) & __float_as_uint(O.s4.z) &
                                __float_as_uint(O.s4.w);
@@ -1798,13 +1668,11 @@ __device__ __forceinline__ void stage_store(const IntegrateArgs& a, const UnitPo
         const int wmx = max(max(O.w4.x, O.w4.y), max(O.w4.z, O.w4.w));
         const bool vals = (s_and == 0x3f800000u) & (s_or == 0x3f800000u) & (wmx < (1 << 23));
         // a lane that did not load its values (per-lane traffic) keeps what the old flag says
-        const bool one = trow ? vals : (O.oflag != 0u);
-        // a lazy line counts one more pending increment; any other update stored the weights
-        // with the pending count folded in: steady (1) or not (0)
-        const unsigned nb = O.lazy ? O.oflag + 1u : (tile_line_all(one) ? 1u : 0u);
+        const bool one = tmask != 0u ? vals : (O.oflag != 0u);
+        const unsigned nb = tile_line_all(one) ? 1u : 0u;  // steady (1) or not (0)
         if (lane_y((int)__lane_id()) == 0 && nb != O.oflag) a.b.sflag[v >> 5] = (uint8_t)nb;
     }
-    if (!FREE && grow) {
+    if (!FREE && gmask != 0u) {
         if (CI32) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) reinterpret_cast<int4*>(a.b.color)[v + k] = O.c32[k];
@@ -1813,7 +1681,7 @@ __device__ __forceinline__ void stage_store(const IntegrateArgs& a, const UnitPo
         }
         if (SEM && gmask) {
             if (hmode == 1u) {
-                st_state<uint4, SEMTSDF_NT_HIST>(a.b.hist + (uint64_t)hlab * g.nvox + v, O.h4);
+                st_state(a.b.hist + (uint64_t)hlab * g.nvox + v, O.h4);
                 // a count that just became 1 sets the bin's bit in the voxel's bin mask (rare
                 // once the surface has been seen: the common path neither reads nor writes it)
                 const unsigned hk[4] = {O.h4.x, O.h4.y, O.h4.z, O.h4.w};
@@ -1915,9 +1783,9 @@ __device__ __forceinline__ UnitPos lane_pos(const UnitGrid& ug, const unsigned* 
     return p;
 }
 
-// Per-lane counts of the count mode (touched and gated voxels, touched lines on lane 0, lazy voxels).
+// Per-lane counts of the count mode (touched and gated voxels, touched lines on lane 0).
 struct Counts {
-    unsigned touch, gate, lines, lazy;
+    unsigned touch, gate, lines;
 };
 
 // Pipeline state carried from one list into the next: the unit whose project, classify and
@@ -1968,21 +1836,11 @@ __device__ __forceinline__ void list_prime(const IntegrateArgs& a, const UnitGri
 // workgroup's dispatch round (blockIdx / CUs: blocks are dealt to the CUs in rounds), so at
 // any time the 4 waves of a SIMD hold distinct priorities and each holds the top one a
 // quarter of the time.
-#ifndef SEMTSDF_PRIO_ROTATE
-#define SEMTSDF_PRIO_ROTATE 1
-#endif
 #ifndef SEMTSDF_PRIO_EVERY
 #define SEMTSDF_PRIO_EVERY 4  // groups per priority step (a power of two); 1 rotated every group (r04)
 #endif
 static_assert((SEMTSDF_PRIO_EVERY & (SEMTSDF_PRIO_EVERY - 1)) == 0, "a power of two");
-#ifndef SEMTSDF_PROBE_SALU
-#define SEMTSDF_PROBE_SALU 0  // instrumentation builds: extra scalar ALU ops per group (issue probe)
-#endif
-#ifndef SEMTSDF_PROBE_VALU
-#define SEMTSDF_PROBE_VALU 0  // instrumentation builds: extra vector ALU ops per group (issue probe)
-#endif
 __device__ __forceinline__ void rotate_prio(unsigned p) {
-    if (!SEMTSDF_PRIO_ROTATE) return;
     switch (p & 3u) {  // s_setprio takes an immediate
         case 0: __builtin_amdgcn_s_setprio(0); break;
         case 1: __builtin_amdgcn_s_setprio(1); break;
@@ -2013,9 +1871,9 @@ __device__ __forceinline__ void integrate_list(const IntegrateArgs& a, const Uni
     if (!S.primed) list_prime<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, KIND>(a, ug, seg_cap, v, S, n);
     unsigned en[kSlots];
     if (v.i + nwaves < v.ngroups) group_entries(v, v.i + nwaves, seg_cap, en);
-    const bool chain = NKIND >= 0 && SEMTSDF_CHAIN && nx->i < nx->ngroups;
+    const bool chain = NKIND >= 0 && nx->i < nx->ngroups;
     unsigned eb[kSlots];
-    if (NKIND >= 0 && SEMTSDF_CHAIN && chain) group_entries(*nx, nx->i, seg_cap, eb);
+    if (chain) group_entries(*nx, nx->i, seg_cap, eb);
     while (v.i + nwaves < v.ngroups) {
         const UnitPos nxt = lane_pos(ug, en);
         if (v.i + 2u * nwaves < v.ngroups) group_entries(v, v.i + 2u * nwaves, seg_cap, en);
@@ -2023,7 +1881,7 @@ __device__ __forceinline__ void integrate_list(const IntegrateArgs& a, const Uni
         stage_compute<SEM, GATE, CI32, VOTE, FREE>(a, s_rcp, S.C, S.L, S.O);
         const StoreMeta Mc = store_meta(S.C);
         stage_classify<SEM, GATE, VOTE, COUNT, FREE>(a, S.P, S.C, true, n.touch, n.gate, n.lines, S.lutv);
-        stage_store<SEM, CI32, VOTE, FREE, COUNT>(a, S.cur, coff, Mc, S.O, n.lazy);
+        stage_store<SEM, CI32, VOTE, FREE>(a, S.cur, coff, Mc, S.O);
         stage_load<SEM, CI32, VOTE, FREE>(a, nxt, coff, S.C, S.L);
         S.cur = nxt;
         v.i += nwaves;
@@ -2032,147 +1890,33 @@ __device__ __forceinline__ void integrate_list(const IntegrateArgs& a, const Uni
         ++S.groups;
         if (SEMTSDF_PRIO_EVERY == 1 || (S.groups & (SEMTSDF_PRIO_EVERY - 1u)) == 0u)
             rotate_prio(S.groups / SEMTSDF_PRIO_EVERY);
-#if SEMTSDF_PROBE_SALU || SEMTSDF_PROBE_VALU
-        {  // issue probes (instrumentation builds only): N extra scalar / vector ALU ops per group
-            unsigned su = S.groups, vu = threadIdx.x;
-#pragma unroll
-            for (int q = 0; q < SEMTSDF_PROBE_SALU; ++q) asm volatile("s_mov_b32 %0, %0" : "+s"(su));
-#pragma unroll
-            for (int q = 0; q < SEMTSDF_PROBE_VALU; ++q) asm volatile("v_add_u32 %0, %0, 1" : "+v"(vu));
-            if (su == 0xFFFFFFFFu && vu == 0xFFFFFFFFu) S.lutv ^= 1u;  // keeps the probes live
-        }
-#endif
     }
     // the wave's last unit of this list
-    if (NKIND >= 0 && SEMTSDF_CHAIN && chain) {
+    if (chain) {
         const UnitPos nxt = lane_pos(ug, eb);
         stage_project<SHARD, PIN, NFREE, NFULL, VOTE>(a, nxt, lane, S.P);
         stage_compute<SEM, GATE, CI32, VOTE, FREE>(a, s_rcp, S.C, S.L, S.O);
         const StoreMeta Mc = store_meta(S.C);
         stage_classify<SEM, GATE, VOTE, COUNT, NFREE>(a, S.P, S.C, true, n.touch, n.gate, n.lines, S.lutv);
-        stage_store<SEM, CI32, VOTE, FREE, COUNT>(a, S.cur, coff, Mc, S.O, n.lazy);
+        stage_store<SEM, CI32, VOTE, FREE>(a, S.cur, coff, Mc, S.O);
         stage_load<SEM, CI32, VOTE, NFREE>(a, nxt, coff, S.C, S.L);
         S.cur = nxt;
         S.primed = true;
     } else {
         stage_compute<SEM, GATE, CI32, VOTE, FREE>(a, s_rcp, S.C, S.L, S.O);
-        stage_store<SEM, CI32, VOTE, FREE, COUNT>(a, S.cur, coff, store_meta(S.C), S.O, n.lazy);
+        stage_store<SEM, CI32, VOTE, FREE>(a, S.cur, coff, store_meta(S.C), S.O);
         S.primed = false;
     }
     v.i += nwaves;
 }
 
-// The last list (general units) with its groups past the first round handed out at run time,
-// software-pipelined like integrate_list.  The wave's first group is its static one (v.i <
-// nwaves, primed by the chain from the list before); groups nwaves .. ngroups - 1 are cut into
-// one slice per XCD and handed out through the XCD's own counter (zeroed by the frame's prepass),
-// so waves that finished their earlier lists early take more of them and the waves end together.
-// The counter of XCD x is only touched by waves running on XCD x (the XCC_ID register), so its
-// atomics are workgroup-scope: performed in that XCD's L2.  Every lane of the wave executes the
-// atomic (lane 0 adds 1, the others 0: no divergent branch, so the compiler counts the atomic
-// among the wave's vector-memory operations in order), and the ticket of the group after next
-// is claimed at the end of an iteration and read after the next compute stage, which waits for
-// the state loads issued before it anyway: the claim's round trip hides under the pipeline.
-#ifndef SEMTSDF_DYN_LAST
-#define SEMTSDF_DYN_LAST 0
-#endif
-template <bool SEM, bool GATE, bool CI32, bool VOTE, bool COUNT, bool SHARD, bool PIN>
-__device__ __forceinline__ void integrate_list_dyn(const IntegrateArgs& a, const UnitGrid& ug, unsigned seg_cap,
-                                                   const float* __restrict__ s_rcp, ListView& v, unsigned nwaves,
-                                                   unsigned* xcd_counters, Pipe& S, Counts& n) {
-    const int lane = threadIdx.x & 63;
-    const unsigned coff = (unsigned)lane_zq(lane) * 32u + (unsigned)lane_y(lane) * 4u;
-    if (v.i >= v.ngroups) return;  // then ngroups <= nwaves: no dynamic group either
-    if (!S.primed) list_prime<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, 0>(a, ug, seg_cap, v, S, n);
-    // HW_REG_XCC_ID (hwreg 20), bits 3:0: the XCD this wave runs on
-    const unsigned xcc = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11))) & 7u;
-    // one slice per (XCD, workgroup slot): a single counter per XCD saturates (same-address L2
-    // atomics serialise), so the waves of an XCD share kDynSub counters
-    const unsigned sub = (blockIdx.x >> 3) & (kDynSub - 1u), sl = xcc * kDynSub + sub, ns = 8u * kDynSub;
-    const unsigned D = v.ngroups - min(v.ngroups, nwaves);
-    const unsigned lo = nwaves + D * sl / ns, cnt = nwaves + D * (sl + 1u) / ns - lo;
-    unsigned* ctr = xcd_counters + sl * kListCountStride;
-    auto claim = [&]() -> unsigned {
-        unsigned r = 0u;
-        if (lane == 0) r = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return r;
-    };
-    unsigned en[kSlots];
-    unsigned t = cnt ? (unsigned)__builtin_amdgcn_readlane((int)claim(), 0) : 0u;
-    bool have = t < cnt;
-    if (have) group_entries(v, lo + t, seg_cap, en);
-    // claimed unconditionally (a claim past the slice only moves its counter further): a
-    // conditional one merges with the loop's previous value, and that copy waits for the atomic
-    unsigned pend = claim();
-    while (have) {
-        const UnitPos nxt = lane_pos(ug, en);
-        stage_project<SHARD, PIN, false, false, VOTE>(a, nxt, lane, S.P);
-        stage_compute<SEM, GATE, CI32, VOTE, false>(a, s_rcp, S.C, S.L, S.O);
-        const unsigned t2 = (unsigned)__builtin_amdgcn_readlane((int)pend, 0);
-        const bool have2 = t2 < cnt;
-        if (have2) group_entries(v, lo + t2, seg_cap, en);
-        const StoreMeta Mc = store_meta(S.C);
-        stage_classify<SEM, GATE, VOTE, COUNT, false>(a, S.P, S.C, true, n.touch, n.gate, n.lines, S.lutv);
-        stage_store<SEM, CI32, VOTE, false, COUNT>(a, S.cur, coff, Mc, S.O, n.lazy);
-        stage_load<SEM, CI32, VOTE, false>(a, nxt, coff, S.C, S.L);
-        pend = claim();
-        S.cur = nxt;
-        have = have2;
-        ++S.groups;
-        if (SEMTSDF_PRIO_EVERY == 1 || (S.groups & (SEMTSDF_PRIO_EVERY - 1u)) == 0u)
-            rotate_prio(S.groups / SEMTSDF_PRIO_EVERY);
-    }
-    stage_compute<SEM, GATE, CI32, VOTE, false>(a, s_rcp, S.C, S.L, S.O);
-    stage_store<SEM, CI32, VOTE, false, COUNT>(a, S.cur, coff, store_meta(S.C), S.O, n.lazy);
-    S.primed = false;
-    v.i = v.ngroups;
-}
-
-// The dynamic tail of the last list: groups first .. first + ntail - 1, cut into one slice per
-// XCD, handed out one at a time through the XCD's own counter (zeroed by the frame's prepass),
-// each group integrated without the software pipeline (its latency is hidden across the waves
-// instead).  The static round-robin shares end unevenly (per CU by up to ~15 % of the kernel:
-// profiles/r05/wave_trace_*.txt); waves that finish theirs early take the tail, so the waves end
-// together.  The counter of XCD x is only touched by waves running on XCD x (the XCC_ID register),
-// so its atomics are workgroup-scope: performed in that XCD's L2 (agent-scope atomics go to memory
-// and serialise at ~20 ns each, 2x slower kernels).  Ticket in lane 0 (the compiler waits for all
-// of the wave's memory operations before using it: nothing else is in flight here).
-#ifndef SEMTSDF_TAIL_PCT
-#define SEMTSDF_TAIL_PCT 0  // percent of the last list's groups handed out dynamically (measured slower at 10-35 %: 0)
-#endif
-template <bool SEM, bool GATE, bool CI32, bool VOTE, bool COUNT, bool SHARD, bool PIN>
-__device__ __forceinline__ void integrate_tail(const IntegrateArgs& a, const UnitGrid& ug, unsigned seg_cap,
-                                               const float* __restrict__ s_rcp, const ListView& v, unsigned first,
-                                               unsigned ntail, unsigned* counters, Pipe& S, Counts& n) {
-    const int lane = threadIdx.x & 63;
-    const unsigned coff = (unsigned)lane_zq(lane) * 32u + (unsigned)lane_y(lane) * 4u;
-    // HW_REG_XCC_ID (hwreg 20), bits 3:0: the XCD this wave runs on
-    const unsigned xcc = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11))) & 7u;
-    const unsigned lo = first + ntail * xcc / 8u, hi = first + ntail * (xcc + 1u) / 8u;
-    unsigned* counter = counters + xcc * kListCountStride;
-    for (;;) {
-        unsigned t = 0u;
-        if (lane == 0) t = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        t = (unsigned)__builtin_amdgcn_readfirstlane((int)t);
-        if (t >= hi - lo) break;
-        unsigned e[kSlots];
-        group_entries(v, lo + t, seg_cap, e);
-        S.cur = lane_pos(ug, e);
-        stage_project<SHARD, PIN, false, false, VOTE>(a, S.cur, lane, S.P);
-        stage_classify<SEM, GATE, VOTE, COUNT, false>(a, S.P, S.C, true, n.touch, n.gate, n.lines, S.lutv);
-        stage_load<SEM, CI32, VOTE, false>(a, S.cur, coff, S.C, S.L);
-        stage_compute<SEM, GATE, CI32, VOTE, false>(a, s_rcp, S.C, S.L, S.O);
-        stage_store<SEM, CI32, VOTE, false, COUNT>(a, S.cur, coff, store_meta(S.C), S.O, n.lazy);
-    }
-}
-
 // Persistent wavefronts over the three live-unit lists of the frame: the full free units, the
 // free units (both sdf/weight only, when the mode allows them), then the general units, the
-// pipeline chained from each list into the next.  A static round-robin share: dynamic
-// schedules (per-XCD device atomics, a whole-CU workgroup sharing an LDS queue) evened the
-// waves' end times but ran slower.
-static_assert(!SEMTSDF_XCD_SPLIT || (!SEMTSDF_DYN_LAST && !SEMTSDF_TAIL_PCT),
-              "the dynamic schedules hand out the whole list (no XCD ranges)");
+// pipeline chained from each list into the next (a wave's last unit of a list overlaps the
+// first unit of its next list).  Each XCD's waves take a contiguous eighth of every list
+// (list_view), in a static round-robin share: dynamic schedules (per-XCD ticket atomics for
+// the last list or its tail, a whole-CU workgroup sharing an LDS queue) evened the waves' end
+// times but ran slower ("Dynamic schedules" and "r05: what was measured and not kept").
 #ifndef SEMTSDF_INTEGRATE_WPE
 #define SEMTSDF_INTEGRATE_WPE 4  // waves per SIMD the register allocation targets (5 spills; measured equal)
 #endif
@@ -2185,13 +1929,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VOTE ? 3 : 
     unsigned long long tr[5] = {0, 0, 0, 0, 0};
     unsigned long long trn = 0;
     const unsigned nwaves = gridDim.x * (blockDim.x >> 6);
-#ifndef SEMTSDF_WAVE_PERM
-#define SEMTSDF_WAVE_PERM 0
-#endif
-    // the wave's slot in the round-robin of the lists; SEMTSDF_WAVE_PERM=1: the 4 waves of a
-    // workgroup take slots nwaves/4 apart, so consecutive (adjacent) groups go to different CUs
-    const unsigned wave = __builtin_amdgcn_readfirstlane(
-        SEMTSDF_WAVE_PERM ? (threadIdx.x >> 6) * gridDim.x + blockIdx.x : blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    // the wave's slot in the round-robin of the lists
+    const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     auto groups_of = [&](unsigned n, unsigned rot_) -> unsigned long long {
         const unsigned ng = (n + kSlots - 1) / kSlots, i0 = (wave + nwaves - rot_ % nwaves) % nwaves;
         return i0 < ng ? (ng - 1u - i0) / nwaves + 1u : 0u;
@@ -2207,12 +1946,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VOTE ? 3 : 
     S.groups = dispatch_round() * SEMTSDF_PRIO_EVERY;
     if (SEM && a.lut) S.lutv = reinterpret_cast<const uint32_t*>(a.lut)[lane];
     const unsigned* cnt = a.list_count;
-    unsigned* tail_counter = a.list_count + kLists * kListSegs * kListCountStride;  // zeroed by the prepass
     const unsigned* lst = a.units;
     unsigned n0;
     unsigned rot0 = 0;
     // XCD split (list_view): the wave's XCD xi and its index wx among the XCD's nwx waves
-    const bool split = SEMTSDF_XCD_SPLIT && (gridDim.x & 7u) == 0u;
+    const bool split = (gridDim.x & 7u) == 0u;
     const unsigned nsp = split ? 8u : 1u, xi = split ? blockIdx.x & 7u : 0u;
     const unsigned wx = split ? __builtin_amdgcn_readfirstlane((blockIdx.x >> 3) * (blockDim.x >> 6) + (threadIdx.x >> 6))
                               : wave;
@@ -2234,8 +1972,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VOTE ? 3 : 
         ListView v1 = list_view(lst, cnt, 1, wx, nwx, 0u, xi, nsp);
         rot0 = (vf.cnt + v1.cnt) % nwx;
         ListView v0 = list_view(lst, cnt, 0, wx, nwx, rot0, xi, nsp);
-        const unsigned tail0 = SEMTSDF_TAIL_PCT ? v0.ngroups * SEMTSDF_TAIL_PCT / 100u : 0u;
-        v0.ngroups -= tail0;  // the static share: groups 0 .. ngroups - tail0 - 1
         if (vf.i < vf.ngroups)
             list_prime<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, 2>(a, ug, seg_cap, vf, S, n);
         else if (v1.i < v1.ngroups)
@@ -2252,12 +1988,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VOTE ? 3 : 
             tr[3] = wall_clock64();
             trn = groups_of(vf.total, 0u) | (groups_of(v1.total, 0u) << 20);
         }
-        if (SEMTSDF_DYN_LAST)
-            integrate_list_dyn<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN>(a, ug, seg_cap, s_rcp, v0, nwaves, tail_counter, S, n);
-        else
-            integrate_list<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, 0, -1>(a, ug, seg_cap, s_rcp, v0, nullptr, nwx, S, n);
-        if (tail0) integrate_tail<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN>(a, ug, seg_cap, s_rcp, v0, v0.ngroups, tail0,
-                                                                           tail_counter, S, n);
+        integrate_list<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, 0, -1>(a, ug, seg_cap, s_rcp, v0, nullptr, nwx, S, n);
         n0 = v0.total;
         if (COUNT && blockIdx.x == 0 && threadIdx.x == 0) {
             atomicAdd(a.counters + 4, (unsigned long long)(v1.total + vf.total));
@@ -2275,44 +2006,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VOTE ? 3 : 
             tab ? (const __attribute__((address_space(4))) unsigned*)a.first_tab - 4 : u4;
         const unsigned pre0[2] = {t4[4u + 2u * wq], t4[5u + 2u * wq]};
         ListView v0 = list_view(lst, cnt, 0, wx, nwx, 0u, xi, nsp);
-        const unsigned tail0 = SEMTSDF_TAIL_PCT ? v0.ngroups * SEMTSDF_TAIL_PCT / 100u : 0u;
-        v0.ngroups -= tail0;
         if (v0.i < v0.ngroups)
             list_prime<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, 0>(a, ug, seg_cap, v0, S, n,
                                                                    (tab || (!split && v0.list == lst + 4)) && wq == wave ? pre0
                                                                                                                 : nullptr);
         __syncthreads();
         if (SEMTSDF_WAVE_TRACE) tr[1] = tr[2] = tr[3] = wall_clock64();
-        if (SEMTSDF_DYN_LAST)
-            integrate_list_dyn<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN>(a, ug, seg_cap, s_rcp, v0, nwaves, tail_counter, S, n);
-        else
-            integrate_list<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, 0, -1>(a, ug, seg_cap, s_rcp, v0, nullptr, nwx, S, n);
-        if (tail0) integrate_tail<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN>(a, ug, seg_cap, s_rcp, v0, v0.ngroups, tail0,
-                                                                           tail_counter, S, n);
+        integrate_list<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, 0, -1>(a, ug, seg_cap, s_rcp, v0, nullptr, nwx, S, n);
         n0 = v0.total;
     }
-#if SEMTSDF_TAIL_CULL_PROBE
-    {  // timing probe (instrumentation builds only): a unit cull of the whole grid as tail work,
-       // tasks of 64 units claimed through the XCD's own counter (zeroed by the prepass); results discarded
-        const unsigned xcc = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11))) & 7u;
-        unsigned* ctr = tail_counter + xcc * kListCountStride;
-        const unsigned ntask = (ug.n + 63u) / 64u;
-        const unsigned nmine = ntask > xcc ? (ntask - xcc + 7u) / 8u : 0u;
-        unsigned acc = 0;
-        for (;;) {
-            unsigned t = 0;
-            if (lane == 0) t = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            t = (unsigned)__builtin_amdgcn_readfirstlane((int)t);
-            if (t >= nmine) break;
-            const unsigned u = (t * 8u + xcc) * 64u + (unsigned)lane;
-            if (u < ug.n) {
-                const unsigned ux = u % ug.nux, r = u / ug.nux, uy = r % ug.nuy, uz = r / ug.nuy;
-                acc += (unsigned)unit_cull(a, (int)ux * UX, (int)uy * UY, (int)uz * UZ);
-            }
-        }
-        if (acc == 0xFFFFFFFFu) a.counters[7] = acc;  // keeps the work live
-    }
-#endif
     if (SEM && a.lut && a.relabel_mask) {  // the frame's mask through the same table, in place
         const unsigned npx = (unsigned)(a.width * a.height);
         const unsigned gid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
@@ -2347,17 +2049,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VOTE ? 3 : 
     }
     if (COUNT) {
         nlive += n0;
-        unsigned long long t = n.touch, gg = n.gate, lz = n.lazy, tl = n.lines;
+        unsigned long long t = n.touch, gg = n.gate, tl = n.lines;
         for (int off = 32; off > 0; off >>= 1) {
             t += __shfl_xor(t, off, 64);
             gg += __shfl_xor(gg, off, 64);
-            lz += __shfl_xor(lz, off, 64);
             tl += __shfl_xor(tl, off, 64);
         }
         if (lane == 0) {
             if (t) atomicAdd(a.counters + 0, t);
             if (gg) atomicAdd(a.counters + 1, gg);
-            if (lz) atomicAdd(a.counters + 6, lz);
             if (tl) atomicAdd(a.counters + 7, tl);
         }
         // live units of both lists
@@ -2426,7 +2126,8 @@ unsigned integrate_pre_waves() {
     // the SfM semantic instantiation (the others run at the same occupancy; where one does not, its
     // waves read their first group the ordinary way: k_integrate compares first_nwaves with its grid)
     static const unsigned w = 4u * resident_grid(k_integrate<true, true, false, false, false, false, true>, 256);
-    return w;
+    // a grid with more wave slots than k_compact_lists writes gets no table (0: read the ordinary way)
+    return w <= kFirstTabSlots ? w : 0u;
 }
 
 hipError_t launch_integrate(const IntegrateArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
@@ -2695,7 +2396,7 @@ __device__ __forceinline__ bool sample_or_skip(const VolGeom& g, const VolBufs& 
                                                float px, float py, float pz, float* f, bool box = false,
                                                int oct = -1) {
     const TriCoord c = tri_coord<SH>(g, px, py, pz);
-    if (OCT || (SEMTSDF_BRICK_DIST && box && b.bdist)) {
+    if (OCT || (box && b.bdist)) {
         // the brick's distance r to the nearest non-skippable brick of the ray's octant: the
         // r^3 bricks from it on towards the ray's direction are skippable, one box for the
         // march to step through (without an octant: the (2r-1)^3 bricks around it)
@@ -2768,9 +2469,6 @@ struct MarchStats {
 #define SEMTSDF_MARCH_SPEC 5
 #endif
 constexpr int kMarchSpec = SEMTSDF_MARCH_SPEC;  // speculative samples per evaluated sample
-#ifndef SEMTSDF_MARCH_PRIO
-#define SEMTSDF_MARCH_PRIO 0u  // iterations after which a marching wave's priority rises (0: off; 8-20 measured 0.5-1.5 % slower, profiles/r04/ab_march_priority.txt)
-#endif
 
 template <bool OCT>
 __device__ bool march_ray(const VolGeom& g, const VolBufs& b, float ox, float oy, float oz, float dx, float dy,
@@ -2782,8 +2480,7 @@ __device__ bool march_ray(const VolGeom& g, const VolBufs& b, float ox, float oy
     SkipCursor cur;
     const RayVox rv = ray_vox(g, ox, oy, oz, dx, dy, dz);
     const bool box = OCT || b.bmin != nullptr;  // single-volume marches only (the host rejects sharded handles)
-    const int oct = OCT || (SEMTSDF_BRICK_OCT && b.boct) ? (dx < 0.0f ? 1 : 0) | (dy < 0.0f ? 2 : 0) | (dz < 0.0f ? 4 : 0)
-                                                         : -1;
+    const int oct = OCT || b.boct ? (dx < 0.0f ? 1 : 0) | (dy < 0.0f ? 2 : 0) | (dz < 0.0f ? 4 : 0) : -1;
     float f_t = 1.0f, f_tt = 0.0f;
     bool prev_skipped = false;  // f_t not evaluated: re-evaluate it at t_prev if needed
     float t_prev = t;
@@ -2800,17 +2497,8 @@ __device__ bool march_ray(const VolGeom& g, const VolBufs& b, float ox, float oy
     // One memory access (a brick lookup or a sample) per iteration; in between, each lane
     // runs through the samples of its current skippable brick with arithmetic only, so the
     // lanes of a wave do not wait for each other's memory round trips sample by sample.
-    unsigned iters = 0;
     while (t < tfar) {
         if (st) st->iters++;
-        // a wave still marching after many iterations holds the kernel's tail: raise its
-        // issue priority (age arbitration would otherwise favour the older, shorter waves)
-        if (SEMTSDF_MARCH_PRIO) {
-            const unsigned wi = __builtin_amdgcn_readfirstlane(++iters);
-            if (wi == SEMTSDF_MARCH_PRIO) __builtin_amdgcn_s_setprio(1);
-            else if (wi == 2u * SEMTSDF_MARCH_PRIO) __builtin_amdgcn_s_setprio(2);
-            else if (wi == 4u * SEMTSDF_MARCH_PRIO) __builtin_amdgcn_s_setprio(3);
-        }
         if (box && cur.skip && in_skip_box(cur, rv, t)) {
             // the same additions as sample-by-sample stepping (the hit position depends on
             // them), tested against the box's exit parameter, then exactly near the exit
@@ -3110,7 +2798,7 @@ __device__ __forceinline__ void assoc_pixel_out(const AssocPixels& px, int npx, 
 
 // The single-volume marches take the octant-map specialisation when the volume has the maps.
 inline bool oct_maps(const VolBufs& b) {
-    return SEMTSDF_BRICK_DIST && SEMTSDF_BRICK_OCT && b.bmin && b.bdist && b.boct;
+    return b.bmin && b.bdist && b.boct;
 }
 
 // One 16x16-pixel tile (bx, by) of the association march, a whole workgroup.
@@ -4190,10 +3878,8 @@ __device__ __forceinline__ bool sample_at_skip(const ShardRayArgs& a, const RayG
         if (br != cur.brick) {
             cur.brick = br;
             int rad = 0;
-            const int oct = SEMTSDF_BRICK_DIST && SEMTSDF_BRICK_OCT && a.b.boct
-                                ? (r.dx < 0.0f ? 1 : 0) | (r.dy < 0.0f ? 2 : 0) | (r.dz < 0.0f ? 4 : 0)
-                                : -1;
-            if (SEMTSDF_BRICK_DIST && a.b.bdist) {
+            const int oct = a.b.boct ? (r.dx < 0.0f ? 1 : 0) | (r.dy < 0.0f ? 2 : 0) | (r.dz < 0.0f ? 4 : 0) : -1;
+            if (a.b.bdist) {
                 rad = oct >= 0 ? (int)reinterpret_cast<const uint8_t*>(a.b.boct)[(size_t)br * 8 + oct] : a.b.bdist[br];
                 cur.skip = rad > 0;
             } else {

@@ -8,7 +8,7 @@
 //   k_read8         8-B/lane streaming read of 512 MiB                     known read 512 MiB
 //   k_read4         4-B/lane streaming read of 512 MiB                     known read 512 MiB
 //   k_rmw16         the integrate's state RMW: 512-B half-tile units of sdf + weight, 16 B per
-//                   lane, default-policy loads, non-temporal stores (SEMTSDF_NT_LOAD 0 / _STORE 1),
+//                   lane, default-policy loads, non-temporal stores,
 //                   two units per wave-iteration, over a live set in the cull's x-run order
 //                                                                           known read = write = units x 1 KiB
 //   k_gather8_lines one 8-B load per distinct 128-B line of a 512 MiB array, lines in a scrambled
