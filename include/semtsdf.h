@@ -352,6 +352,48 @@ typedef struct semtsdf_surface_point {
 int semtsdf_export_surface(semtsdf_vol* v, float sdf_max, int32_t min_weight, semtsdf_surface_point* out,
                            uint64_t capacity, uint64_t* count);
 
+/* ---- mesh extraction (no reference counterpart) ----------------------------------------------
+ * The labelled triangle mesh of the sdf = 0 level set: marching tetrahedra on the Kuhn split.
+ * Cells: the cube with min corner (x, y, z), 0 <= x < Dx-1, 0 <= y < Dy-1, 0 <= z < Dz-1 (global
+ *   z), is valid iff all 8 corners have weight >= min_weight.  A corner is negative iff sdf < 0.0f
+ *   (+0.0 and -0.0 are not).
+ * Tetrahedra: 6 per cell, one per axis permutation (a, b, c), indexed by its lexicographic rank
+ *   (xyz, xzy, yxz, yzx, zxy, zyx): v0 = the corner, v1 = v0 + e_a, v2 = v1 + e_b, v3 = v2 + e_c.
+ * Edges, vertices: a tet edge (vi, vj), i < j, is named by its owner voxel vi and its class
+ *   dx | dy << 1 | dz << 2 (1..7) of the offset vj - vi.  There is one mesh vertex per edge that an
+ *   emitted triangle references, shared by all triangles using it.
+ * Triangles of a tet with k negative vertices: none for k = 0, 4; for k = 1, 3 one on the three
+ *   edges at the lone vertex; for k = 2, negatives A < B and others C < D in tet vertex order,
+ *   (AC, AD, BD) and (AC, BD, BC).  Each is wound so that, with every crossing at its edge midpoint
+ *   in index space, the right-hand normal points from the negative towards the non-negative
+ *   vertices (into free space).  Degenerate triangles (a crossing on a voxel) are kept.
+ * Position: s0 the owner's sdf, s1 the other endpoint's; t = s0 / (s0 - s1); per axis a,
+ *   g = (float)index[a] + (d[a] ? t : 0.0f), pos[a] = g * voxel[a] + vol_start[a]: f32, one rounding
+ *   per operation, a multiply then an add (not the fmaf of the voxel position rule tsdf.cu:30,
+ *   from which it differs by at most 1 ulp at t = 0).
+ * Attributes: colour (int32 colours clamped to [0, 255]) and label (histogram argmax, first
+ *   maximum; 0 without a count or in a volume that is not SEMANTIC) of the endpoint nearer the
+ *   surface: the owner if |s0| <= |s1|, else the other one.
+ * Outputs are host pointers; the call synchronises.  verts == NULL && tris == NULL: count only
+ * (one NULL alone is SEMTSDF_ERR_INVALID).  With both given and a capacity short:
+ * SEMTSDF_ERR_INVALID, the counts written, the buffers untouched.  2^32 vertices or more:
+ * SEMTSDF_ERR_UNSUPPORTED.  Scratch (29 B per 256 stored voxels to count, 4 B per stored voxel
+ * more to emit, and the outputs) lives for the call; failing to get it is SEMTSDF_ERR_OOM and the
+ * handle stays usable.  The volume is not modified.  The output is deterministic: two calls on
+ * one state return identical bytes; the order is otherwise unspecified (canonical: vertices by
+ * (x, y, z, edge)).  A shard extracts the cells whose min-corner plane it owns (keys carry the
+ * global z), so the vertices on a chunk's halo plane appear in both neighbouring shards with
+ * identical bytes; welding equal keys joins the shards' meshes into the whole volume's. */
+typedef struct semtsdf_mesh_vertex { /* 32 bytes */
+    float pos[3];
+    uint32_t x, y, z;       /* owner voxel, global index */
+    uint8_t r, g, b, label;
+    uint8_t edge, pad[3];   /* class 1..7; pad = 0 */
+} semtsdf_mesh_vertex;
+int semtsdf_extract_mesh(semtsdf_vol* v, int32_t min_weight, semtsdf_mesh_vertex* verts, uint64_t vcap,
+                         uint32_t* tris /* 3 per triangle */, uint64_t tcap /* triangles */,
+                         uint64_t* nverts, uint64_t* ntris);
+
 /* ---- empty-space maps (tests) ------------------------------------------------------------
  * The octant distance map of the current volume state, one word per 8^3 brick (x-major, z
  * fastest): byte o = the octant-o distance in bricks (0: the brick is not skippable).  count =

@@ -2091,6 +2091,80 @@ int semtsdf_export_surface(semtsdf_vol* v, float sdf_max, int32_t min_weight, se
     return SEMTSDF_OK;
 }
 
+int semtsdf_extract_mesh(semtsdf_vol* v, int32_t min_weight, semtsdf_mesh_vertex* verts, uint64_t vcap, uint32_t* tris,
+                         uint64_t tcap, uint64_t* nverts, uint64_t* ntris) {
+    static_assert(sizeof(semtsdf_mesh_vertex) == sizeof(MeshVertexRec) && sizeof(MeshVertexRec) == 32,
+                  "mesh vertex layout");
+    if (!v || !nverts || !ntris) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
+    if (!verts != !tris) return fail(SEMTSDF_ERR_INVALID, "verts and tris must both be given or both be NULL");
+    HIPC(hipSetDevice(v->device));
+    hipStream_t s = v->stream;
+    if (int rc = after_bmin(v, s)) return rc;
+    const uint64_t nb = mesh_blocks(v->g);
+    // scratch of the call, one allocation per pass: 29 B per 256-voxel tile to count; 4 B per stored
+    // voxel and the outputs to emit
+    char* count_d = nullptr;
+    char* emit_d = nullptr;
+    auto done = [&](int rc) {
+        if (count_d) (void)hipFree(count_d);
+        if (emit_d) (void)hipFree(emit_d);
+        return rc;
+    };
+    auto alloc = [&](char** p, uint64_t bytes) {
+        const hipError_t e = hipMalloc((void**)p, bytes);
+        if (e == hipSuccess) return SEMTSDF_OK;
+        *p = nullptr;
+        (void)hipGetLastError();  // the handle stays usable
+        return fail(e == hipErrorOutOfMemory ? SEMTSDF_ERR_OOM : SEMTSDF_ERR_HIP, "mesh scratch hipMalloc(%llu): %s",
+                    (unsigned long long)bytes, hipGetErrorString(e));
+    };
+    uint64_t off = 0;
+    auto carve = [&](uint64_t bytes) {  // 256-B aligned parts of one allocation
+        const uint64_t at = off;
+        off += (bytes + 255u) & ~(uint64_t)255u;
+        return at;
+    };
+    const uint64_t o_tot = carve(2 * sizeof(unsigned long long)), o_cnt = carve(nb * sizeof(uint2)),
+                   o_gsum = carve(mesh_groups(v->g) * 2 * sizeof(unsigned long long)),
+                   o_list = carve(mesh_list_words(v->g) * sizeof(uint32_t)), o_base = carve(nb * sizeof(ulonglong2));
+    if (int rc = alloc(&count_d, off)) return done(rc);
+    unsigned long long* tot_d = (unsigned long long*)(count_d + o_tot);
+    uint2* cnt_d = (uint2*)(count_d + o_cnt);
+    unsigned long long* gsum_d = (unsigned long long*)(count_d + o_gsum);
+    uint32_t* alist_d = (uint32_t*)(count_d + o_list);
+    ulonglong2* base_d = (ulonglong2*)(count_d + o_base);
+    unsigned long long tot[2] = {0, 0};
+    uint32_t listed[2] = {0, 0};  // blocks and tiles the emit pass runs over
+    hipError_t e = launch_mesh_count(v->g, v->b, min_weight, cnt_d, gsum_d, alist_d, base_d, tot_d, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(tot, tot_d, sizeof(tot), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(listed, alist_d, sizeof(listed), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return done(fail(SEMTSDF_ERR_HIP, "mesh count: %s", hipGetErrorString(e)));
+    *nverts = tot[0];
+    *ntris = tot[1];
+    if (tot[0] >= (1ull << 32))
+        return done(fail(SEMTSDF_ERR_UNSUPPORTED, "mesh of %llu vertices: indices are 32-bit", tot[0]));
+    if (!verts) return done(SEMTSDF_OK);
+    if (vcap < tot[0] || tcap < tot[1])
+        return done(fail(SEMTSDF_ERR_INVALID, "mesh of %llu vertices and %llu triangles exceeds the capacities %llu, %llu",
+                         tot[0], tot[1], (unsigned long long)vcap, (unsigned long long)tcap));
+    if (tot[0] == 0) return done(SEMTSDF_OK);  // no vertex, hence no triangle
+    off = 0;
+    const uint64_t o_vtab = carve(v->g.nvox * sizeof(uint32_t)), o_verts = carve(tot[0] * sizeof(MeshVertexRec)),
+                   o_tris = carve(tot[1] * 3 * sizeof(uint32_t));
+    if (int rc = alloc(&emit_d, off)) return done(rc);
+    uint32_t* vtab_d = (uint32_t*)(emit_d + o_vtab);
+    MeshVertexRec* verts_d = (MeshVertexRec*)(emit_d + o_verts);
+    uint32_t* tris_d = (uint32_t*)(emit_d + o_tris);
+    e = launch_mesh_emit(v->g, v->b, min_weight, v->color_wide ? 1 : 0, (v->p.flags & SEMTSDF_F_SEMANTIC) ? 1 : 0, cnt_d,
+                         alist_d, listed[0], listed[1], base_d, vtab_d, verts_d, tris_d, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(verts, verts_d, tot[0] * sizeof(MeshVertexRec), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(tris, tris_d, tot[1] * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return done(fail(SEMTSDF_ERR_HIP, "mesh emit: %s", hipGetErrorString(e)));
+    return done(SEMTSDF_OK);
+}
+
 int semtsdf_set_instrumentation(semtsdf_vol* v, int enable) {
     if (!v) return fail(SEMTSDF_ERR_INVALID, "NULL handle");
     v->instr = enable;

@@ -394,4 +394,39 @@ struct SurfacePoint {  // one exported surface voxel (semtsdf_surface_point)
 hipError_t launch_export_surface(const VolGeom& g, const VolBufs& b, float sdf_max, int min_w, int color_wide,
                                  int semantic, SurfacePoint* out, uint64_t cap, unsigned long long* count, hipStream_t s);
 
+// Mesh extraction (semtsdf_extract_mesh): count, scan, emit over the 256-voxel storage tiles.
+// Tile b = the voxels b * 256 .. b * 256 + 255, one thread each; a block of the count and vertex
+// passes takes the tiles of kMeshXB consecutive x layers (it reads kMeshXB + 2 layers for them,
+// where a block per tile reads 3 for 1).  Scratch:
+//   cnt   [tiles]       vertices owned by / triangles of the cells of the tile
+//   gsum  [groups * 2]  sums of cnt over groups of kMeshGroup tiles (vertices, triangles)
+//   alist [2 + ...]     work lists of the emit pass: the numbers of listed blocks and tiles, the
+//                       blocks with a nonzero count, the tiles with a triangle (in any order: the
+//                       place of every tile's output is fixed by base)
+//   base  [tiles]       exclusive sums of cnt (x: vertices, y: triangles); tot[0..1]: the totals
+//   vtab  [g.nvox]      per voxel: bit 0 cell valid, bits 1..7 the active owned edges by class,
+//                       bits 8..18 vertices owned by lower threads of the tile, bits 19..26 the
+//                       signs of the cell's corners (written for tiles with a nonzero count only)
+struct MeshVertexRec {  // semtsdf_mesh_vertex as two 16-B stores
+    uint4 a;            // pos[3] bits, x
+    uint4 b;            // y, z, r | g << 8 | b << 16 | label << 24, edge class
+};
+constexpr int kMeshXB = 4;
+constexpr unsigned kMeshGroup = 4096;  // tiles per block of the scan: 256 threads x 16
+__host__ __device__ inline uint64_t mesh_blocks(const VolGeom& g) { return g.nvox / 256u; }  // tiles
+inline uint64_t mesh_groups(const VolGeom& g) { return (mesh_blocks(g) + kMeshGroup - 1) / kMeshGroup; }
+__host__ __device__ inline uint32_t mesh_classify_blocks(const VolGeom& g) {
+    return (uint32_t)((g.dimx + kMeshXB - 1) / kMeshXB) * g.nuy * g.nuz;
+}
+inline uint64_t mesh_list_words(const VolGeom& g) { return 2u + mesh_classify_blocks(g) + mesh_blocks(g); }
+template <typename T>
+__host__ __device__ inline T* mesh_list_blocks(const VolGeom&, T* alist) { return alist + 2; }
+template <typename T>
+__host__ __device__ inline T* mesh_list_tiles(const VolGeom& g, T* alist) { return alist + 2 + mesh_classify_blocks(g); }
+hipError_t launch_mesh_count(const VolGeom& g, const VolBufs& b, int min_w, uint2* cnt, unsigned long long* gsum,
+                             uint32_t* alist, ulonglong2* base, unsigned long long* tot, hipStream_t s);
+hipError_t launch_mesh_emit(const VolGeom& g, const VolBufs& b, int min_w, int color_wide, int semantic,
+                            const uint2* cnt, const uint32_t* alist, unsigned nblocks, unsigned ntiles,
+                            const ulonglong2* base, uint32_t* vtab, MeshVertexRec* verts, uint32_t* tris, hipStream_t s);
+
 }  // namespace semtsdf

@@ -4599,4 +4599,366 @@ hipError_t launch_export_surface(const VolGeom& g, const VolBufs& b, float sdf_m
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------
+// Mesh extraction (no reference counterpart): marching tetrahedra on the Kuhn split of every
+// valid cell, the contract of semtsdf_extract_mesh (include/semtsdf.h, DESIGN.md "Mesh
+// extraction").  Count, scan, emit: every block and thread has a fixed place in the output,
+// so two calls return the same bytes.
+//   k_mesh_classify<0>  per tile: vertices owned by its voxels, triangles of its cells
+//   k_mesh_scan         exclusive sums of the tile counts
+//   k_mesh_classify<1>  the same classification again: per-voxel table + the vertices
+//   k_mesh_triangles    triangles, indices through the per-voxel tables of the 7 owners
+// (scratch and work lists: semtsdf_internal.h)
+// ------------------------------------------------------------------------------------
+// Tet t = the axis permutation of lexicographic rank t; v[t][i] the cube corner (x | y << 1 |
+// z << 2) of its vertex i; per sign case (bit i: vertex i negative) n triangles of 3 edges,
+// an edge coded owner corner | class << 3, wound by the midpoint rule.
+struct MeshTable {
+    uint8_t v[6][4];
+    uint8_t n[6][16];
+    uint8_t e[6][16][6];
+    int bad;
+};
+
+constexpr MeshTable make_mesh_table() {
+    MeshTable T{};
+    const int perms[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+    for (int t = 0; t < 6; ++t) {
+        int V[4][3] = {};
+        for (int i = 0; i < 3; ++i) {
+            for (int a = 0; a < 3; ++a) V[i + 1][a] = V[i][a];
+            V[i + 1][perms[t][i]] += 1;
+        }
+        for (int i = 0; i < 4; ++i) T.v[t][i] = (uint8_t)(V[i][0] | V[i][1] << 1 | V[i][2] << 2);
+        for (int s = 0; s < 16; ++s) {
+            int neg[4] = {}, pos[4] = {}, nn = 0, np = 0;
+            for (int i = 0; i < 4; ++i) {
+                if (s >> i & 1) neg[nn++] = i;
+                else pos[np++] = i;
+            }
+            int tri[2][3][2] = {};
+            int nt = 0;
+            if (nn == 1) {
+                for (int k = 0; k < 3; ++k) { tri[0][k][0] = neg[0]; tri[0][k][1] = pos[k]; }
+                nt = 1;
+            } else if (nn == 3) {
+                for (int k = 0; k < 3; ++k) { tri[0][k][0] = pos[0]; tri[0][k][1] = neg[k]; }
+                nt = 1;
+            } else if (nn == 2) {
+                const int A = neg[0], B = neg[1], C = pos[0], D = pos[1];
+                const int q[2][3][2] = {{{A, C}, {A, D}, {B, D}}, {{A, C}, {B, D}, {B, C}}};
+                for (int j = 0; j < 2; ++j)
+                    for (int k = 0; k < 3; ++k) { tri[j][k][0] = q[j][k][0]; tri[j][k][1] = q[j][k][1]; }
+                nt = 2;
+            }
+            T.n[t][s] = (uint8_t)nt;
+            // (centroid of the non-negative vertices - centroid of the negative ones) * nn * np
+            int want[3] = {};
+            for (int a = 0; a < 3; ++a) {
+                for (int i = 0; i < np; ++i) want[a] += V[pos[i]][a] * nn;
+                for (int i = 0; i < nn; ++i) want[a] -= V[neg[i]][a] * np;
+            }
+            for (int j = 0; j < nt; ++j) {
+                int m[3][3] = {};  // edge midpoints, doubled
+                for (int k = 0; k < 3; ++k)
+                    for (int a = 0; a < 3; ++a) m[k][a] = V[tri[j][k][0]][a] + V[tri[j][k][1]][a];
+                int p[3] = {}, q[3] = {};
+                for (int a = 0; a < 3; ++a) { p[a] = m[1][a] - m[0][a]; q[a] = m[2][a] - m[0][a]; }
+                const int nrm[3] = {p[1] * q[2] - p[2] * q[1], p[2] * q[0] - p[0] * q[2], p[0] * q[1] - p[1] * q[0]};
+                const int dot = nrm[0] * want[0] + nrm[1] * want[1] + nrm[2] * want[2];
+                if (dot == 0) T.bad = 1;
+                for (int k = 0; k < 3; ++k) {
+                    const int kk = dot > 0 || k == 0 ? k : 3 - k;  // flip: swap the last two
+                    const int i0 = tri[j][kk][0], i1 = tri[j][kk][1];
+                    const int lo = i0 < i1 ? i0 : i1, hi = i0 < i1 ? i1 : i0;
+                    T.e[t][s][j * 3 + k] = (uint8_t)(T.v[t][lo] | (T.v[t][lo] ^ T.v[t][hi]) << 3);
+                }
+            }
+        }
+    }
+    return T;
+}
+static_assert(make_mesh_table().bad == 0, "mesh table: a triangle without an orientation");
+__constant__ MeshTable kMesh = make_mesh_table();
+
+constexpr int kMeshHY = 10;  // halo rows: y0 - 1 .. y0 + 8
+constexpr int kMeshHZ = 40;  // halo planes: z0 - 4 .. z0 + 35 in whole 16-B groups (z0 - 1 .. z0 + 32 used)
+
+// Exclusive sum of `val` over the 256 threads of the block (s_w: 4 words); total in *tot.
+__device__ __forceinline__ unsigned mesh_block_scan(unsigned val, unsigned* s_w, unsigned* tot) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    unsigned incl = val;
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned n = __shfl_up(incl, off);
+        if (lane >= off) incl += n;
+    }
+    if (lane == 63) s_w[w] = incl;
+    __syncthreads();
+    unsigned pre = 0, t = 0;
+    for (int i = 0; i < 4; ++i) {
+        const unsigned c = s_w[i];
+        pre += i < w ? c : 0u;
+        t += c;
+    }
+    __syncthreads();
+    *tot = t;
+    return pre + incl - val;
+}
+
+__device__ __forceinline__ unsigned mesh_tet_case(unsigned signs, int t) {
+    unsigned s = 0;
+    for (int i = 0; i < 4; ++i) s |= ((signs >> kMesh.v[t][i]) & 1u) << i;
+    return s;
+}
+
+// r | g << 8 | b << 16 | label << 24 of stored voxel t, as k_export_surface exports them
+__device__ __forceinline__ unsigned mesh_voxel_rgbl(const VolGeom& g, const VolBufs& b, uint32_t t, int color_wide,
+                                                    int semantic) {
+    unsigned r, gg, bb;
+    if (color_wide) {
+        const int4 c = reinterpret_cast<const int4*>(b.color)[t];
+        r = (unsigned)min(max(c.x, 0), 255); gg = (unsigned)min(max(c.y, 0), 255); bb = (unsigned)min(max(c.z, 0), 255);
+    } else {
+        const unsigned c = reinterpret_cast<const uint32_t*>(b.color)[t];
+        r = c & 0xFFu; gg = (c >> 8) & 0xFFu; bb = (c >> 16) & 0xFFu;
+    }
+    unsigned lab = 0, best = 0;
+    if (semantic) {
+        unsigned bins = b.hmask[t];
+        while (bins) {
+            const int k = __ffs((int)bins) - 1;
+            bins &= bins - 1u;
+            const unsigned c = b.hist[(uint64_t)k * g.nvox + t];
+            if (c > best) { best = c; lab = (unsigned)k; }
+        }
+    }
+    return r | (gg << 8) | (bb << 16) | (lab << 24);
+}
+
+template <int EMIT>
+__global__ __launch_bounds__(256) void k_mesh_classify(VolGeom g, VolBufs b, int min_w, int color_wide, int semantic,
+                                                       uint2* __restrict__ cnt, unsigned long long* __restrict__ gsum,
+                                                       uint32_t* __restrict__ alist, const ulonglong2* __restrict__ base,
+                                                       uint32_t* __restrict__ vtab, MeshVertexRec* __restrict__ verts) {
+    constexpr int NL = kMeshXB + 2;                // x layers in reach: x0 - 1 .. x0 + kMeshXB
+    __shared__ uint8_t s_f[NL][kMeshHY][kMeshHZ];  // bit 0: stored, weight >= min_w; bit 1: sdf < 0
+    __shared__ float s_s[EMIT ? NL : 1][EMIT ? kMeshHY : 1][EMIT ? kMeshHZ : 1];
+    __shared__ uint8_t s_cv[kMeshXB + 1][9][36];   // cell (x0 - 1 + i, y0 - 1 + j, z0 - 1 + k) is extracted
+    __shared__ unsigned s_w[4];
+    const unsigned tid = threadIdx.x;
+    const unsigned tiles_x = g.nuz * g.nuy;        // tiles per x layer; tile of layer x: x * tiles_x + tyz
+    // the emit pass runs over the blocks the count pass listed (mesh_list_blocks)
+    const unsigned bid = EMIT ? mesh_list_blocks(g, alist)[blockIdx.x] : blockIdx.x;
+    const unsigned tyz = bid % tiles_x;
+    const int zt = (int)(tyz % g.nuz), yt = (int)(tyz / g.nuz), x0 = (int)(bid / tiles_x) * kMeshXB;
+    const int nx = min(kMeshXB, g.dimx - x0);
+    const int y0 = yt * 8, z0 = zt * 32;
+    int has_neg = 0, has_pos = 0;
+    for (int i = (int)tid; i < NL * kMeshHY * kMeshHZ; i += 256) {
+        const int dx = i / (kMeshHY * kMeshHZ), r = i - dx * (kMeshHY * kMeshHZ);
+        const int zg = r / (kMeshHY * 4), r2 = r - zg * (kMeshHY * 4);
+        const int hy = r2 >> 2, hz = zg * 4 + (r2 & 3);
+        const int X = x0 + dx - 1, Y = y0 - 1 + hy, L = z0 - 4 + hz;
+        unsigned f = 0;
+        float s = 0.0f;
+        if (hz >= 3 && hz <= 36 && X >= 0 && X < g.dimx && Y >= 0 && Y < g.dimy && L >= 0 && L < g.lz &&
+            local_to_global_z(g, L) < g.dimz) {
+            const uint32_t t = tile_index(g, X, Y, L);
+            s = b.sdf[t];
+            const unsigned ok = b.wt[t] >= min_w ? 1u : 0u, ng = s < 0.0f ? 1u : 0u;
+            f = ok | (ng << 1);
+            has_neg |= (int)(ok & ng);
+            has_pos |= (int)(ok & (ng ^ 1u));
+        }
+        s_f[dx][hy][hz] = (uint8_t)f;
+        if constexpr (EMIT != 0) s_s[dx][hy][hz] = s;
+    }
+    // no sign change among the usable voxels in reach: no triangle, no vertex
+    const int any_neg = __syncthreads_or(has_neg);
+    const int any_pos = __syncthreads_or(has_pos);
+    if (!any_neg || !any_pos) {
+        if (!EMIT && (int)tid < nx) cnt[(unsigned)(x0 + (int)tid) * tiles_x + tyz] = make_uint2(0u, 0u);
+        return;
+    }
+    const int per = g.chunk + g.halo;
+    for (int i = (int)tid; i < (kMeshXB + 1) * 9 * 33; i += 256) {
+        const int cx = i / (9 * 33), r = i - cx * (9 * 33);
+        const int cy = r / 33, cz = r - cy * 33;
+        const int L = z0 - 1 + cz;  // a shard extracts the cells whose min-corner plane it owns
+        unsigned v = (L >= 0 && (g.nshards == 1 || (L % per) < g.chunk)) ? 1u : 0u;
+        for (int p = 0; p < 8; ++p) v &= s_f[cx + (p & 1)][cy + ((p >> 1) & 1)][3 + cz + (p >> 2)];
+        s_cv[cx][cy][cz] = (uint8_t)v;
+    }
+    __syncthreads();
+    const int zi = (int)((tid >> 5) * 4 + (tid & 3)), yi = (int)((tid >> 2) & 7);  // voxel (x, y0 + yi, z0 + zi)
+    const int hy = yi + 1, hz = zi + 4;
+    bool listed = false;
+    for (int j = 0; j < nx; ++j) {  // the tile of layer x: its place in s_f is j + 1, its cells' in s_cv j + 1
+        const int x = x0 + j;
+        const unsigned blk = (unsigned)x * tiles_x + tyz;
+        if (EMIT) {
+            const uint2 c = cnt[blk];
+            if ((c.x | c.y) == 0u) continue;
+        }
+        unsigned signs = 0;
+        for (int p = 0; p < 8; ++p)
+            signs |= ((unsigned)(s_f[j + 1 + (p & 1)][hy + ((p >> 1) & 1)][hz + (p >> 2)] >> 1) & 1u) << p;
+        const unsigned valid = s_cv[j + 1][yi + 1][zi + 1];
+        unsigned mask = 0;  // bit c: the owned edge of class c is a mesh vertex
+        for (int c = 1; c < 8; ++c) {
+            if ((((signs >> c) ^ signs) & 1u) == 0u) continue;
+            const int ex = c & 1, ey = (c >> 1) & 1, ez = c >> 2;
+            unsigned any = 0;  // the cells holding the edge: min corner at, or along the edge's zero axes one below, the owner
+            for (int mx = ex; mx < 2; ++mx)
+                for (int my = ey; my < 2; ++my)
+                    for (int mz = ez; mz < 2; ++mz) any |= s_cv[j + mx][yi + my][zi + mz];
+            mask |= any << c;
+        }
+        unsigned ntri = 0;
+        if (valid)
+            for (int t = 0; t < 6; ++t) ntri += kMesh.n[t][mesh_tet_case(signs, t)];
+        const unsigned nv = (unsigned)__popc(mask);
+        unsigned tot;
+        const unsigned pre = mesh_block_scan(nv | (ntri << 16), s_w, &tot);  // <= 7 * 256 and 12 * 256
+        if constexpr (!EMIT) {
+            if (tid == 0) {
+                cnt[blk] = make_uint2(tot & 0xFFFFu, tot >> 16);
+                if (tot) {  // integer sums: the same whatever the order of the additions
+                    atomicAdd(&gsum[2u * (blk / kMeshGroup)], (unsigned long long)(tot & 0xFFFFu));
+                    atomicAdd(&gsum[2u * (blk / kMeshGroup) + 1u], (unsigned long long)(tot >> 16));
+                }
+                // work lists of the emit pass; their order does not reach the output, where every
+                // tile's place is fixed by the scan
+                if (tot >> 16) mesh_list_tiles(g, alist)[atomicAdd(&alist[1], 1u)] = blk;
+                if (tot && !listed) {
+                    listed = true;
+                    mesh_list_blocks(g, alist)[atomicAdd(&alist[0], 1u)] = bid;
+                }
+            }
+        } else {
+            const uint32_t t0 = blk * 256u + tid;
+            vtab[t0] = valid | mask | ((pre & 0xFFFFu) << 8) | (signs << 19);
+            const int y = y0 + yi, l = z0 + zi;
+            const int gz = local_to_global_z(g, l);
+            uint64_t vi = base[blk].x + (pre & 0xFFFFu);
+            const float s0 = s_s[j + 1][hy][hz];
+            for (int c = 1; c < 8; ++c) {
+                if (!((mask >> c) & 1u)) continue;
+                const int ex = c & 1, ey = (c >> 1) & 1, ez = c >> 2;
+                const float s1 = s_s[j + 1 + ex][hy + ey][hz + ez];
+                // one rounding per operation; a multiply then an add, not the voxel rule's fmaf
+                const float t = __fdiv_rn(s0, __fsub_rn(s0, s1));
+                const float px = __fadd_rn(__fmul_rn(__fadd_rn((float)x, ex ? t : 0.0f), g.voxel[0]), g.start[0]);
+                const float py = __fadd_rn(__fmul_rn(__fadd_rn((float)y, ey ? t : 0.0f), g.voxel[1]), g.start[1]);
+                const float pz = __fadd_rn(__fmul_rn(__fadd_rn((float)gz, ez ? t : 0.0f), g.voxel[2]), g.start[2]);
+                const bool own = fabsf(s0) <= fabsf(s1);  // attributes of the endpoint nearer the surface
+                const uint32_t ta = own ? t0 : tile_index(g, x + ex, y + ey, l + ez);
+                const unsigned rgbl = mesh_voxel_rgbl(g, b, ta, color_wide, semantic);
+                MeshVertexRec rec;
+                rec.a = make_uint4(__float_as_uint(px), __float_as_uint(py), __float_as_uint(pz), (unsigned)x);
+                rec.b = make_uint4((unsigned)y, (unsigned)gz, rgbl, (unsigned)c);
+                verts[vi++] = rec;
+            }
+        }
+    }
+}
+
+// Exclusive sums of the tile counts.  Block i takes group i of kMeshGroup tiles, 16 consecutive
+// tiles per thread: the sums of the groups before it (gsum, added up by the count pass), then
+// a scan of its own tiles.  The last block writes the totals.
+__global__ __launch_bounds__(256) void k_mesh_scan(const uint2* __restrict__ cnt,
+                                                   const unsigned long long* __restrict__ gsum,
+                                                   ulonglong2* __restrict__ base, unsigned nb,
+                                                   unsigned long long* __restrict__ tot) {
+    __shared__ unsigned s_w[4];
+    __shared__ unsigned long long s_r[2][256];
+    const unsigned tid = threadIdx.x;
+    unsigned long long cv = 0, ct = 0;
+    for (unsigned i = tid; i < blockIdx.x; i += 256u) { cv += gsum[2u * i]; ct += gsum[2u * i + 1u]; }
+    s_r[0][tid] = cv;
+    s_r[1][tid] = ct;
+    __syncthreads();
+    for (unsigned h = 128u; h > 0u; h >>= 1) {
+        if (tid < h) { s_r[0][tid] += s_r[0][tid + h]; s_r[1][tid] += s_r[1][tid + h]; }
+        __syncthreads();
+    }
+    cv = s_r[0][0];
+    ct = s_r[1][0];
+    const unsigned i0 = blockIdx.x * (unsigned)kMeshGroup + tid * 16u;
+    unsigned sv = 0, st = 0;
+    for (unsigned k = 0; k < 16u; ++k)
+        if (i0 + k < nb) { const uint2 c = cnt[i0 + k]; sv += c.x; st += c.y; }
+    unsigned tv, tt;
+    unsigned long long pv = cv + mesh_block_scan(sv, s_w, &tv);  // <= 256 * 16 * 1792 < 2^32
+    unsigned long long pt = ct + mesh_block_scan(st, s_w, &tt);
+    for (unsigned k = 0; k < 16u; ++k)
+        if (i0 + k < nb) {
+            const uint2 c = cnt[i0 + k];
+            base[i0 + k] = make_ulonglong2(pv, pt);
+            pv += c.x; pt += c.y;
+        }
+    if (blockIdx.x == gridDim.x - 1u && tid == 0u) { tot[0] = cv + tv; tot[1] = ct + tt; }
+}
+
+// One block per listed tile (the tiles with a triangle).
+__global__ __launch_bounds__(256) void k_mesh_triangles(VolGeom g, const uint32_t* __restrict__ alist,
+                                                        const ulonglong2* __restrict__ base,
+                                                        const uint32_t* __restrict__ vtab, uint32_t* __restrict__ tris) {
+    __shared__ uint32_t s_first[7][256];  // per owner corner: index of its first vertex
+    __shared__ uint8_t s_mask[7][256];    // and its active classes
+    __shared__ unsigned s_w[4];
+    const unsigned blk = mesh_list_tiles(g, alist)[blockIdx.x], tid = threadIdx.x;
+    const uint32_t w = vtab[blk * 256u + tid];
+    const unsigned signs = (w >> 19) & 0xFFu;
+    unsigned ntri = 0;
+    if (w & 1u)
+        for (int t = 0; t < 6; ++t) ntri += kMesh.n[t][mesh_tet_case(signs, t)];
+    unsigned tot;
+    const unsigned pre = mesh_block_scan(ntri, s_w, &tot);
+    if (!ntri) return;
+    const int zt = (int)(blk % g.nuz), yt = (int)((blk / g.nuz) % g.nuy), x = (int)(blk / (g.nuz * g.nuy));
+    const int y = yt * 8 + (int)((tid >> 2) & 7), l = zt * 32 + (int)((tid >> 5) * 4 + (tid & 3));
+    for (int p = 0; p < 7; ++p) {  // a valid cell: all 8 corners are stored voxels
+        const uint32_t t = tile_index(g, x + (p & 1), y + ((p >> 1) & 1), l + (p >> 2));
+        const uint32_t wp = vtab[t];
+        s_first[p][tid] = (uint32_t)(base[t >> 8].x + ((wp >> 8) & 0x7FFu));
+        s_mask[p][tid] = (uint8_t)(wp & 0xFEu);
+    }
+    uint64_t ti = (base[blk].y + pre) * 3u;
+    for (int t = 0; t < 6; ++t) {
+        const unsigned s = mesh_tet_case(signs, t);
+        const unsigned n = kMesh.n[t][s];
+        for (unsigned j = 0; j < n * 3u; ++j) {
+            const unsigned e = kMesh.e[t][s][j];
+            const unsigned p = e & 7u, c = e >> 3;
+            tris[ti++] = s_first[p][tid] + (unsigned)__popc(s_mask[p][tid] & ((1u << c) - 1u));
+        }
+    }
+}
+
+hipError_t launch_mesh_count(const VolGeom& g, const VolBufs& b, int min_w, uint2* cnt, unsigned long long* gsum,
+                             uint32_t* alist, ulonglong2* base, unsigned long long* tot, hipStream_t s) {
+    const unsigned nb = (unsigned)mesh_blocks(g), ng = (unsigned)mesh_groups(g);
+    hipError_t e = hipMemsetAsync(gsum, 0, (size_t)ng * 2 * sizeof(unsigned long long), s);
+    if (e == hipSuccess) e = hipMemsetAsync(alist, 0, 2 * sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_mesh_classify<0>, dim3(mesh_classify_blocks(g)), dim3(256), 0, s, g, b, min_w, 0, 0, cnt, gsum,
+                       alist, (const ulonglong2*)nullptr, (uint32_t*)nullptr, (MeshVertexRec*)nullptr);
+    hipLaunchKernelGGL(k_mesh_scan, dim3(ng), dim3(256), 0, s, (const uint2*)cnt, (const unsigned long long*)gsum, base,
+                       nb, tot);
+    return hipGetLastError();
+}
+
+hipError_t launch_mesh_emit(const VolGeom& g, const VolBufs& b, int min_w, int color_wide, int semantic,
+                            const uint2* cnt, const uint32_t* alist, unsigned nblocks, unsigned ntiles,
+                            const ulonglong2* base, uint32_t* vtab, MeshVertexRec* verts, uint32_t* tris, hipStream_t s) {
+    if (nblocks > mesh_classify_blocks(g) || ntiles > mesh_blocks(g)) return hipErrorInvalidValue;
+    if (nblocks)
+        hipLaunchKernelGGL(k_mesh_classify<1>, dim3(nblocks), dim3(256), 0, s, g, b, min_w, color_wide, semantic,
+                           const_cast<uint2*>(cnt), (unsigned long long*)nullptr, const_cast<uint32_t*>(alist), base, vtab,
+                           verts);
+    if (ntiles) hipLaunchKernelGGL(k_mesh_triangles, dim3(ntiles), dim3(256), 0, s, g, alist, base, vtab, tris);
+    return hipGetLastError();
+}
+
 }  // namespace semtsdf

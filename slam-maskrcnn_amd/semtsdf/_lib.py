@@ -105,6 +105,12 @@ class SurfacePoint(C.Structure):
                 ("r", C.c_uint8), ("g", C.c_uint8), ("b", C.c_uint8), ("label", C.c_uint8)]
 
 
+class MeshVertex(C.Structure):
+    _fields_ = [("pos", C.c_float * 3), ("x", C.c_uint32), ("y", C.c_uint32), ("z", C.c_uint32),
+                ("r", C.c_uint8), ("g", C.c_uint8), ("b", C.c_uint8), ("label", C.c_uint8),
+                ("edge", C.c_uint8), ("pad", C.c_uint8 * 3)]
+
+
 class Timing(C.Structure):
     _fields_ = [
         ("integrate_ms", C.c_double),
@@ -187,6 +193,8 @@ SIGNATURES = {
     "semtsdf_download_slab": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "semtsdf_upload": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "semtsdf_export_surface": (_I, [_P, _F, C.c_int32, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "semtsdf_extract_mesh": (_I, [_P, C.c_int32, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64),
+                                  C.POINTER(C.c_uint64)]),
     "semtsdf_map_words": (_I, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "semtsdf_set_instrumentation": (_I, [_P, _I]),
     "semtsdf_get_timing": (_I, [_P, C.POINTER(Timing)]),
