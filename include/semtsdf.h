@@ -394,6 +394,60 @@ int semtsdf_extract_mesh(semtsdf_vol* v, int32_t min_weight, semtsdf_mesh_vertex
                          uint32_t* tris /* 3 per triangle */, uint64_t tcap /* triangles */,
                          uint64_t* nverts, uint64_t* ntris);
 
+/* ---- instance inventory and id remapping (no reference counterpart) ----------------------------
+ * semtsdf_instance_stats: what the semantic map contains, per instance id, in one read-only pass.
+ * Selection: exactly that of semtsdf_export_surface -- every stored voxel this handle owns (a
+ *   shard: its owned planes; never a halo plane, never the y/z padding of the tiled storage, never
+ *   a plane with global z >= Dz) with weight >= min_weight and |sdf| < sdf_max (normalised units).
+ * Label of a selected voxel: the argmax of its histogram, first maximum; 0 without a count.  So
+ *   the sum of out[k].voxels over k equals semtsdf_export_surface's count for the same arguments.
+ * out[k], 0 <= k < 32: see the fields below; sums run over the selected voxels labelled k, except
+ *   `support`, which counts the selected voxels whose bin k is nonzero (labelled k or not).
+ * overlap (optional, 32 x 32 u64, row-major): overlap[a * 32 + b] = the selected voxels in which
+ *   bins a and b are both nonzero; symmetric, its diagonal is `support`.  NULL: not computed.
+ * Everything is an integer, so the result does not depend on the order of accumulation: two calls
+ *   on one state return identical bytes, and the shards' results add up (sums; min/max for the
+ *   boxes) to the single volume's.  Outputs are host pointers; the call synchronises; the volume is
+ *   not modified; scratch (11 KB) lives for the call.  A volume without SEMTSDF_F_SEMANTIC:
+ *   SEMTSDF_ERR_UNSUPPORTED.  NULL v or out, or !(sdf_max > 0): SEMTSDF_ERR_INVALID, decided before
+ *   any device work. */
+typedef struct semtsdf_instance {   /* 96 bytes */
+    uint64_t voxels;      /* selected voxels whose label is this id */
+    uint64_t votes;       /* sum over those voxels of the winning bin's count */
+    uint64_t support;     /* selected voxels whose bin of this id is nonzero (= overlap[id][id]) */
+    uint64_t sum[3];      /* sums of the global voxel index (x, y, z) over `voxels` */
+    uint64_t rgb_sum[3];  /* sums of the colour (int32 colours clamped to [0, 255]) over `voxels` */
+    uint32_t min[3], max[3]; /* index bounding box of `voxels`; voxels == 0: min = UINT32_MAX, max = 0 */
+} semtsdf_instance;
+int semtsdf_instance_stats(semtsdf_vol* v, float sdf_max, int32_t min_weight,
+                           semtsdf_instance out[SEMTSDF_MAX_OBJECTS], uint64_t* overlap /* [32*32] or NULL */);
+/* semtsdf_remap_instances: the histogram through a lookup table, in place: merge, drop, compact ids.
+ * For every stored voxel of the handle (halo planes included, so shards given the same table stay
+ *   consistent with their neighbours): hist'[j] = sum of hist[k] over the k with lut[k] == j (u32,
+ *   modulo 2^32); the bin mask the samplers use is rebuilt (bin j present iff hist'[j] != 0).  sdf,
+ *   weight, colour, the steady flags, the empty-space maps and n_obs are untouched.
+ * lut: lut[k] < 32 for every k and lut[0] == 0 (background stays background).  Any other id may map
+ *   to 0 (dissolved into the background), to another id (merged) or to itself; cycles (a <-> b) are
+ *   legal: every source bin of a voxel is read before any of its bins is written.
+ * num_objs: -1 keeps the handle's next id; otherwise it becomes the next id (written in stream
+ *   order) and, with cur the current one, must satisfy
+ *     1 + max{lut[k] : 0 <= k < max(1, min(cur, 32))} <= num_objs <= max(cur, 1)
+ *   (with -1 the left inequality is checked against max(cur, 1): no live id may map past the ids
+ *   in use).  A violation of this or of the table rules: SEMTSDF_ERR_INVALID, nothing applied.
+ * A volume without SEMTSDF_F_SEMANTIC: SEMTSDF_ERR_UNSUPPORTED.  The remap is queued on `stream`
+ *   (NULL: the handle's own) as an integrate is: after the last empty-space map update and, in
+ *   stream order, after the frame work queued before it (a frame's lagged view and deferred mask
+ *   relabel are queued with that frame); readers on other streams are the caller's to order, as
+ *   for semtsdf_parse_frame_dev_after.  The call itself reads the current next id, so it waits for
+ *   the work queued before it on `stream`; it does not wait for the remap.  An identity table
+ *   launches no kernel but still applies num_objs.
+ * Merging is safe for the association: a voxel receives at most one vote per integrated frame, so
+ *   the sum of any set of its bins is at most n_obs; a merged count therefore never exceeds what the
+ *   reference could have produced, and the positive-term path of the association (a count above
+ *   n_obs) is not triggered by a merge. */
+int semtsdf_remap_instances(semtsdf_vol* v, const uint8_t lut[SEMTSDF_MAX_OBJECTS], int32_t num_objs,
+                            void* stream);
+
 /* ---- empty-space maps (tests) ------------------------------------------------------------
  * The octant distance map of the current volume state, one word per 8^3 brick (x-major, z
  * fastest): byte o = the octant-o distance in bricks (0: the brick is not skippable).  count =

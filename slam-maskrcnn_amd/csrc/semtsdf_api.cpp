@@ -2165,6 +2165,70 @@ int semtsdf_extract_mesh(semtsdf_vol* v, int32_t min_weight, semtsdf_mesh_vertex
     return done(SEMTSDF_OK);
 }
 
+int semtsdf_instance_stats(semtsdf_vol* v, float sdf_max, int32_t min_weight, semtsdf_instance* out,
+                           uint64_t* overlap) {
+    static_assert(sizeof(semtsdf_instance) == sizeof(InstanceRec) && sizeof(InstanceRec) == 96, "instance layout");
+    if (!v || !out) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
+    if (!(sdf_max > 0.0f)) return fail(SEMTSDF_ERR_INVALID, "sdf_max must be > 0");
+    if (!(v->p.flags & SEMTSDF_F_SEMANTIC)) return fail(SEMTSDF_ERR_UNSUPPORTED, "instance stats need a SEMANTIC volume");
+    HIPC(hipSetDevice(v->device));
+    hipStream_t s = v->stream;
+    if (int rc = after_bmin(v, s)) return rc;
+    constexpr size_t rec_bytes = kMaxObjects * sizeof(InstanceRec), ov_bytes = kMaxObjects * kMaxObjects * sizeof(uint64_t);
+    char* scratch = nullptr;  // the records, then the overlap table
+    hipError_t e = hipMalloc((void**)&scratch, rec_bytes + ov_bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // the handle stays usable
+        return fail(e == hipErrorOutOfMemory ? SEMTSDF_ERR_OOM : SEMTSDF_ERR_HIP, "instance stats scratch: %s",
+                    hipGetErrorString(e));
+    }
+    unsigned long long* ov_d = overlap ? (unsigned long long*)(scratch + rec_bytes) : nullptr;
+    e = launch_instance_stats(v->g, v->b, sdf_max, min_weight, v->color_wide ? 1 : 0, (InstanceRec*)scratch, ov_d, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, scratch, rec_bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && overlap) e = hipMemcpyAsync(overlap, ov_d, ov_bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(scratch);
+    if (e != hipSuccess) return fail(SEMTSDF_ERR_HIP, "instance stats: %s", hipGetErrorString(e));
+    return SEMTSDF_OK;
+}
+
+int semtsdf_remap_instances(semtsdf_vol* v, const uint8_t* lut, int32_t num_objs, void* stream) {
+    if (!v || !lut) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
+    if (lut[0] != 0) return fail(SEMTSDF_ERR_INVALID, "lut[0] must be 0 (background stays background)");
+    RemapLut L{};
+    uint32_t moved = 0;
+    for (int k = 0; k < kMaxObjects; ++k) {
+        if (lut[k] >= kMaxObjects) return fail(SEMTSDF_ERR_INVALID, "lut[%d] = %d is not an id below %d", k, lut[k], kMaxObjects);
+        L.w[k >> 3] |= (unsigned long long)lut[k] << ((k & 7) * 8);
+        if (lut[k] != k) moved |= 1u << k;
+    }
+    if (num_objs < -1) return fail(SEMTSDF_ERR_INVALID, "num_objs must be -1 or an id count");
+    if (!(v->p.flags & SEMTSDF_F_SEMANTIC)) return fail(SEMTSDF_ERR_UNSUPPORTED, "remap needs a SEMANTIC volume");
+    HIPC(hipSetDevice(v->device));
+    hipStream_t s = pick(v, stream);
+    // a deferred mask relabel lives only inside a frame call (consumed by its integrate, or applied
+    // by relabel_unconsumed when that fails); one left standing would carry ids of before the remap
+    if (v->pending_lut) return fail(SEMTSDF_ERR_STATE, "a frame's deferred relabel is pending");
+    // the volume's writer, ordered as the integrate is: after the last empty-space map update;
+    // the frame work queued before it on s (a lagged view and the association march read the
+    // histogram in the launches of parse_frame_view_dev) precedes it in stream order
+    if (int rc = after_bmin(v, s)) return rc;
+    // the current next id lives on the device (the decisions advance it there)
+    int cur = 0;
+    HIPC(hipMemcpyAsync(&cur, v->num_objs_d, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    const int live = std::max(1, std::min(cur, kMaxObjects)), top = std::max(cur, 1);
+    int need = 1;
+    for (int k = 0; k < live; ++k) need = std::max(need, 1 + (int)lut[k]);
+    if (need > (num_objs < 0 ? top : num_objs))
+        return fail(SEMTSDF_ERR_INVALID, "the table maps a live id to %d, past the ids in use (num_objs %d)", need - 1,
+                    num_objs < 0 ? cur : num_objs);
+    if (num_objs > top) return fail(SEMTSDF_ERR_INVALID, "num_objs %d exceeds the current %d", num_objs, cur);
+    HIPC(launch_remap_instances(v->g, v->b, L, moved, s));
+    if (num_objs >= 0) HIPC(hipMemsetD32Async((hipDeviceptr_t)v->num_objs_d, num_objs, 1, s));
+    return SEMTSDF_OK;
+}
+
 int semtsdf_set_instrumentation(semtsdf_vol* v, int enable) {
     if (!v) return fail(SEMTSDF_ERR_INVALID, "NULL handle");
     v->instr = enable;

@@ -429,4 +429,21 @@ hipError_t launch_mesh_emit(const VolGeom& g, const VolBufs& b, int min_w, int c
                             const uint2* cnt, const uint32_t* alist, unsigned nblocks, unsigned ntiles,
                             const ulonglong2* base, uint32_t* vtab, MeshVertexRec* verts, uint32_t* tris, hipStream_t s);
 
+// Instance inventory (semtsdf_instance_stats): one pass over the tiled storage, a wave per
+// 256-voxel tile, per-block sums in LDS, one flush of the nonzero entries per block.
+struct InstanceRec {  // semtsdf_instance
+    unsigned long long voxels, votes, support, sum[3], rgb_sum[3];
+    uint32_t min[3], max[3];
+};
+// rec: [kMaxObjects], cleared by the launcher (sums 0, min UINT32_MAX, max 0); overlap: [32 * 32]
+// or nullptr (not computed), cleared too.
+hipError_t launch_instance_stats(const VolGeom& g, const VolBufs& b, float sdf_max, int min_w, int color_wide,
+                                 InstanceRec* rec, unsigned long long* overlap, hipStream_t s);
+// Histogram remap (semtsdf_remap_instances): lut packed 8 ids per word (id k: byte k & 7 of word
+// k >> 3); moved: bit k set when lut[k] != k (nonzero).
+struct RemapLut {
+    unsigned long long w[4];
+};
+hipError_t launch_remap_instances(const VolGeom& g, const VolBufs& b, RemapLut lut, uint32_t moved, hipStream_t s);
+
 }  // namespace semtsdf

@@ -4961,4 +4961,189 @@ hipError_t launch_mesh_emit(const VolGeom& g, const VolBufs& b, int min_w, int c
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------
+// Instance inventory (no reference counterpart): the contract of semtsdf_instance_stats
+// (include/semtsdf.h, DESIGN.md "Instance inventory").  The selection is k_export_surface's, but
+// the walk is the storage's: a wave takes one 256-voxel tile, a lane the 4 z-consecutive voxels
+// of one 16-B vector of sdf and of wt, so the wave reads whole 128-B lines and (x, y, z) come
+// from the tile (wave-uniform: scalar divisions) and the lane.  hmask, colour and histogram are
+// read for the selected voxels only.  Integer sums throughout: the result does not depend on the
+// order of the atomics.
+// ------------------------------------------------------------------------------------
+constexpr int kInstSums = 9;  // the u64 sums leading InstanceRec
+static_assert(offsetof(InstanceRec, min) == kInstSums * 8 && sizeof(InstanceRec) == 96, "InstanceRec layout");
+constexpr unsigned kInstBlocks = 2048;  // persistent grid: 8 blocks of 4 waves on each of 256 CUs
+
+__global__ __launch_bounds__(256) void k_instance_clear(InstanceRec* __restrict__ rec,
+                                                        unsigned long long* __restrict__ overlap) {
+    const unsigned tid = threadIdx.x;
+    if (tid < kMaxObjects) {
+        InstanceRec r{};
+        r.min[0] = r.min[1] = r.min[2] = 0xFFFFFFFFu;
+        rec[tid] = r;
+    }
+    if (overlap)
+        for (unsigned i = tid; i < kMaxObjects * kMaxObjects; i += 256u) overlap[i] = 0ull;
+}
+
+__global__ __launch_bounds__(256) void k_instance_stats(VolGeom g, VolBufs b, float sdf_max, int min_w, int color_wide,
+                                                        InstanceRec* __restrict__ rec,
+                                                        unsigned long long* __restrict__ overlap) {
+    // per block: the sums as u64 (votes and index sums are not bounded by the voxel count); the
+    // overlap counters as u32: a block adds at most 1 per voxel to each and the whole volume has
+    // fewer than 2^32 stored voxels (checked at create), so they cannot overflow
+    __shared__ unsigned long long s_sum[kMaxObjects][kInstSums];
+    __shared__ unsigned s_min[kMaxObjects][3], s_max[kMaxObjects][3];
+    __shared__ unsigned s_ov[kMaxObjects * kMaxObjects];
+    const unsigned tid = threadIdx.x;
+    for (unsigned i = tid; i < kMaxObjects * kInstSums; i += 256u) (&s_sum[0][0])[i] = 0ull;
+    for (unsigned i = tid; i < kMaxObjects * 3; i += 256u) { (&s_min[0][0])[i] = 0xFFFFFFFFu; (&s_max[0][0])[i] = 0u; }
+    for (unsigned i = tid; i < kMaxObjects * kMaxObjects; i += 256u) s_ov[i] = 0u;
+    __syncthreads();
+    const unsigned ntiles = (unsigned)(g.nvox >> 8), tiles_x = g.nuy * g.nuz;
+    const unsigned lane = tid & 63u;
+    const int yi = (int)(lane & 7u), zq = (int)(lane >> 3);  // the lane's vector: row yi, planes 4 zq .. 4 zq + 3 of the tile
+    const int per = g.chunk + g.halo;
+    for (unsigned tile = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (tid >> 6)); tile < ntiles;
+         tile += gridDim.x * 4u) {
+        const uint32_t t0 = tile * 256u + lane * 4u;
+        const float4 s4 = reinterpret_cast<const float4*>(b.sdf)[t0 >> 2];
+        const int4 w4 = reinterpret_cast<const int4*>(b.wt)[t0 >> 2];
+        const float sv[4] = {s4.x, s4.y, s4.z, s4.w};
+        const int wv[4] = {w4.x, w4.y, w4.z, w4.w};
+        unsigned sel = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sel |= (wv[j] >= min_w && fabsf(sv[j]) < sdf_max ? 1u : 0u) << j;
+        if (!sel) continue;
+        const unsigned x = tile / tiles_x, r = tile - x * tiles_x;
+        const unsigned yt = r / g.nuz, zt = r - yt * g.nuz;
+        const int y = (int)yt * 8 + yi;
+        if (y >= g.dimy) continue;  // y padding
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (!((sel >> j) & 1u)) continue;
+            const int l = (int)zt * 32 + zq * 4 + j;
+            if (l >= g.lz) continue;                                     // z padding
+            if (g.nshards > 1 && (l % per) >= g.chunk) continue;          // halo plane: its owner counts it
+            const int gz = local_to_global_z(g, l);
+            if (gz >= g.dimz) continue;
+            const uint32_t t = t0 + (uint32_t)j;
+            const unsigned bins = b.hmask[t];
+            unsigned lab = 0, best = 0;
+            for (unsigned m = bins; m; m &= m - 1u) {
+                const int k = __ffs((int)m) - 1;
+                const unsigned c = b.hist[(uint64_t)k * g.nvox + t];
+                if (c > best) { best = c; lab = (unsigned)k; }
+                atomicAdd(&s_sum[k][2], 1ull);  // support
+                if (overlap)
+                    for (unsigned m2 = bins; m2; m2 &= m2 - 1u) atomicAdd(&s_ov[k * kMaxObjects + (__ffs((int)m2) - 1)], 1u);
+            }
+            unsigned cr, cg, cb;
+            if (color_wide) {
+                const int4 c = reinterpret_cast<const int4*>(b.color)[t];
+                cr = (unsigned)min(max(c.x, 0), 255); cg = (unsigned)min(max(c.y, 0), 255); cb = (unsigned)min(max(c.z, 0), 255);
+            } else {
+                const unsigned c = reinterpret_cast<const uint32_t*>(b.color)[t];
+                cr = c & 0xFFu; cg = (c >> 8) & 0xFFu; cb = (c >> 16) & 0xFFu;
+            }
+            unsigned long long* a = s_sum[lab];
+            atomicAdd(&a[0], 1ull);
+            atomicAdd(&a[1], (unsigned long long)best);
+            atomicAdd(&a[3], (unsigned long long)x);
+            atomicAdd(&a[4], (unsigned long long)y);
+            atomicAdd(&a[5], (unsigned long long)gz);
+            atomicAdd(&a[6], (unsigned long long)cr);
+            atomicAdd(&a[7], (unsigned long long)cg);
+            atomicAdd(&a[8], (unsigned long long)cb);
+            atomicMin(&s_min[lab][0], x); atomicMin(&s_min[lab][1], (unsigned)y); atomicMin(&s_min[lab][2], (unsigned)gz);
+            atomicMax(&s_max[lab][0], x); atomicMax(&s_max[lab][1], (unsigned)y); atomicMax(&s_max[lab][2], (unsigned)gz);
+        }
+    }
+    __syncthreads();
+    // one flush per block, the nonzero entries only
+    for (unsigned i = tid; i < kMaxObjects * kInstSums; i += 256u) {
+        const unsigned long long v = (&s_sum[0][0])[i];
+        if (v) atomicAdd(reinterpret_cast<unsigned long long*>(&rec[i / kInstSums]) + i % kInstSums, v);
+    }
+    if (tid < kMaxObjects * 3) {
+        const unsigned k = tid / 3u, a = tid - k * 3u;
+        if (s_min[k][a] != 0xFFFFFFFFu) {  // the block saw a voxel of this label
+            atomicMin(&rec[k].min[a], s_min[k][a]);
+            atomicMax(&rec[k].max[a], s_max[k][a]);
+        }
+    }
+    if (overlap)
+        for (unsigned i = tid; i < kMaxObjects * kMaxObjects; i += 256u)
+            if (s_ov[i]) atomicAdd(&overlap[i], (unsigned long long)s_ov[i]);
+}
+
+hipError_t launch_instance_stats(const VolGeom& g, const VolBufs& b, float sdf_max, int min_w, int color_wide,
+                                 InstanceRec* rec, unsigned long long* overlap, hipStream_t s) {
+    hipLaunchKernelGGL(k_instance_clear, dim3(1), dim3(256), 0, s, rec, overlap);
+    const uint64_t blocks = ((g.nvox >> 8) + 3u) / 4u;
+    if (blocks)
+        hipLaunchKernelGGL(k_instance_stats, dim3((unsigned)(blocks < kInstBlocks ? blocks : kInstBlocks)), dim3(256), 0, s,
+                           g, b, sdf_max, min_w, color_wide, rec, overlap);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// Histogram remap (semtsdf_remap_instances): hist'[j] = sum of hist[k] over lut[k] == j, in
+// place, one thread per stored voxel in tile order (256 consecutive words of every plane).  A
+// voxel none of whose present bins moves leaves having read its hmask word.  Otherwise every
+// source bin of the voxel is read (into the thread's column of an LDS table, summed by
+// destination) before any of its bins is written: with a <-> b, plane a is a destination and a
+// source.  The loops run over the bins any lane of the wave needs, so the plane is wave-uniform
+// and the loads and stores are coalesced; a thread reads and writes its own voxel only.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned remap_lut(const RemapLut& L, int k) {  // selects: no indexed register array
+    const unsigned long long w = k < 16 ? (k < 8 ? L.w[0] : L.w[1]) : (k < 24 ? L.w[2] : L.w[3]);
+    return (unsigned)(w >> ((k & 7) * 8)) & 0xFFu;
+}
+
+__global__ __launch_bounds__(256) void k_remap_instances(VolGeom g, uint32_t* hist, uint32_t* __restrict__ hmask,
+                                                         RemapLut L, uint32_t moved) {
+    __shared__ uint32_t s_acc[kMaxObjects][256];  // per thread: the new count of every destination bin
+    const unsigned tid = threadIdx.x;
+    // nvox is a multiple of 256: the lanes of a wave leave the loop together
+    for (uint64_t t = (uint64_t)blockIdx.x * 256u + tid; t < g.nvox; t += (uint64_t)gridDim.x * 256u) {
+        const unsigned m = hmask[t];
+        const unsigned act = m & moved;  // present bins that move
+        if (!__any(act != 0u)) continue;
+        unsigned dst = 0;  // their destinations
+        for (int k = 0; k < kMaxObjects; ++k) {
+            s_acc[k][tid] = 0u;
+            if (!__any((act >> k) & 1u)) continue;
+            const unsigned d = 1u << remap_lut(L, k);
+            if ((act >> k) & 1u) dst |= d;
+        }
+        // sources: the moving bins and the present bins that stay and receive (lut[k] == k)
+        const unsigned src = act | (m & dst & ~moved);
+        for (int k = 0; k < kMaxObjects; ++k) {
+            if (!__any((src >> k) & 1u)) continue;
+            const unsigned j = remap_lut(L, k);
+            if ((src >> k) & 1u) s_acc[j][tid] += hist[(uint64_t)k * g.nvox + t];
+        }
+        const unsigned touched = act | dst;  // emptied sources and destinations
+        unsigned nm = m & ~touched;
+        for (int j = 0; j < kMaxObjects; ++j) {
+            if (!__any((touched >> j) & 1u)) continue;
+            if ((touched >> j) & 1u) {
+                const unsigned c = s_acc[j][tid];
+                hist[(uint64_t)j * g.nvox + t] = c;
+                nm |= (c != 0u ? 1u : 0u) << j;
+            }
+        }
+        if (act) hmask[t] = nm;
+    }
+}
+
+hipError_t launch_remap_instances(const VolGeom& g, const VolBufs& b, RemapLut lut, uint32_t moved, hipStream_t s) {
+    if (!b.hist || !b.hmask || g.nvox == 0 || moved == 0u) return hipSuccess;
+    const uint64_t blocks = g.nvox >> 8;
+    hipLaunchKernelGGL(k_remap_instances, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, s, g, b.hist,
+                       b.hmask, lut, moved);
+    return hipGetLastError();
+}
+
 }  // namespace semtsdf

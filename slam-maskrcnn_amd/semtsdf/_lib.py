@@ -111,6 +111,11 @@ class MeshVertex(C.Structure):
                 ("edge", C.c_uint8), ("pad", C.c_uint8 * 3)]
 
 
+class Instance(C.Structure):
+    _fields_ = [("voxels", C.c_uint64), ("votes", C.c_uint64), ("support", C.c_uint64), ("sum", C.c_uint64 * 3),
+                ("rgb_sum", C.c_uint64 * 3), ("min", C.c_uint32 * 3), ("max", C.c_uint32 * 3)]
+
+
 class Timing(C.Structure):
     _fields_ = [
         ("integrate_ms", C.c_double),
@@ -195,6 +200,8 @@ SIGNATURES = {
     "semtsdf_export_surface": (_I, [_P, _F, C.c_int32, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "semtsdf_extract_mesh": (_I, [_P, C.c_int32, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64),
                                   C.POINTER(C.c_uint64)]),
+    "semtsdf_instance_stats": (_I, [_P, _F, C.c_int32, _P, _P]),
+    "semtsdf_remap_instances": (_I, [_P, _P, C.c_int32, _P]),
     "semtsdf_map_words": (_I, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "semtsdf_set_instrumentation": (_I, [_P, _I]),
     "semtsdf_get_timing": (_I, [_P, C.POINTER(Timing)]),

@@ -2,8 +2,8 @@
 
 `Configuration` keeps the reference's two static knobs with the same names and values
 (src/SfM_CUDA/configuration.h:2-9).  `duplicate_thresh` is declared there but never read
-by the reference; it is kept (and passed through the C ABI) for drop-in compatibility and
-is unused here too.  The remaining constants are the hard-coded values SURVEY.md §8a
+by the reference; it is kept (and passed through the C ABI) for drop-in compatibility, and
+its one reader here is TSDF.prune_instances (the default duplicate test).  The remaining constants are the hard-coded values SURVEY.md §8a
 (row a10) lists, each with its reference location.
 """
 from __future__ import annotations

@@ -277,6 +277,19 @@ class LocalShardGroup:
         for v, m in zip(self.vols, mask_ptrs):  # each integrate advances its handle's n_obs (ABI 12)
             v.integrate_dev(depth_ptr, rgb_ptr, m, E, self.stream)
 
+    def instance_stats(self, sdf_max: float = 0.2, min_weight: int = 1, overlap: bool = True) -> dict:
+        """The whole volume's instance stats: every shard reports its owned planes, the host adds
+        them up (semtsdf.instances.merge_instance_stats)."""
+        from .instances import merge_instance_stats
+
+        return merge_instance_stats([v.instance_stats(sdf_max, min_weight, overlap) for v in self.vols])
+
+    def remap_instances(self, lut, num_objs: int = -1):
+        """The same table on every shard (halo planes included, so neighbours stay identical)."""
+        for v in self.vols:
+            v.remap_instances(lut, num_objs, self._s())
+        self.vols[0].sync()  # readers on the shards' own streams (instance_stats, download) follow
+
 
 def _sum_int32_dev(ptrs, out_ptr, n, stream):
     """out = sum of the int32 vectors at ptrs (device), via host staging (tests only)."""

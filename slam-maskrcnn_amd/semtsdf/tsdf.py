@@ -216,6 +216,25 @@ class TSDF:
             return None
         return self._shape(self.vol.download(sdf=False, wt=False, color=False, cls=True)["cls_cnt"])
 
+    # ------------------------------------------------------------------ instances
+    def instances(self, sdf_max: float = 0.2, min_weight: int = 1, overlap: bool = True) -> dict:
+        """What the map contains, per instance id (semtsdf.instances.instance_stats)."""
+        return self.vol.instance_stats(sdf_max, min_weight, overlap)
+
+    def prune_instances(self, min_voxels: int = 0, duplicate_thresh: float | None = None, sdf_max: float = 0.2,
+                        min_weight: int = 1):
+        """Merges duplicate ids (support IoU above duplicate_thresh; default: the configuration's
+        Configuration::duplicate_thresh), dissolves ids with fewer than min_voxels surface voxels
+        into the background and renumbers the rest 1..m, in place.  Returns (lut, num_objs): the
+        table applied (old id -> new id) and the new next id."""
+        from .instances import plan_remap
+
+        thr = self.config.duplicate_thresh if duplicate_thresh is None else duplicate_thresh
+        st = self.vol.instance_stats(sdf_max, min_weight, overlap=True)
+        lut, num = plan_remap(st, self.num_objs, duplicate_thresh=thr, min_voxels=min_voxels, compact=True)
+        self.vol.remap_instances(lut, num)
+        return lut, num
+
     # ------------------------------------------------------------------ raycast (a8)
     def render(self, angle: float, mode: str = "label", dist: float | None = None):
         """Viewer::show_tsdf (viewer.cu:137-179) without the window: BGR u8 image."""

@@ -279,6 +279,24 @@ class Volume:
                 c(cls, np.int32), c(cls_cnt, np.int32)]
         L.check(L.load().semtsdf_upload(self._h, *[L.ptr(a) for a in arrs]))
 
+    # ---- instance inventory and id remapping
+    def instance_stats(self, sdf_max: float = 0.2, min_weight: int = 1, overlap: bool = True) -> dict:
+        """Per-instance voxel counts, votes, supports, index and colour sums, boxes and the
+        overlap table of this (semantic) volume: semtsdf.instances.instance_stats."""
+        from .instances import instance_stats
+
+        return instance_stats(self, sdf_max, min_weight, overlap)
+
+    def remap_instances(self, lut, num_objs: int = -1, stream=None):
+        """The histogram through `lut` (32 ids; lut[0] == 0) in place, merging, dropping or
+        renumbering ids; num_objs (-1: unchanged) becomes the next id (semtsdf_remap_instances;
+        queued on `stream`, None: the volume's own)."""
+        t = np.ascontiguousarray(np.asarray(lut).reshape(-1))
+        if t.size != L.MAX_OBJECTS or (t < 0).any() or (t > 255).any():
+            raise ValueError(f"lut must hold {L.MAX_OBJECTS} ids")
+        t = t.astype(np.uint8)
+        L.check(L.load().semtsdf_remap_instances(self._h, L.ptr(t), int(num_objs), stream))
+
     # ---- instrumentation
     def set_instrumentation(self, events: bool = True, count: bool = False, force_exact: bool = False,
                             other_map_passes: bool = False, frame_fold: bool = False):
