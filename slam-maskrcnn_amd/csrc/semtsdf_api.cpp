@@ -25,16 +25,6 @@
 
 using namespace semtsdf;
 
-#ifndef SEMTSDF_EVENT_FLAGS_DEFAULT
-#define SEMTSDF_EVENT_FLAGS_DEFAULT 2  // order_event_flags(): 0 system-scope release, 1 device-scope release, 2 no system fence
-#endif
-#ifndef SEMTSDF_FRAME_FOLD_DEFAULT
-#define SEMTSDF_FRAME_FOLD_DEFAULT 0  // env SEMTSDF_FRAME_FOLD=0/1 overrides (A/B)
-#endif
-#ifndef SEMTSDF_MARCH_LPT_DEFAULT
-#define SEMTSDF_MARCH_LPT_DEFAULT 1  // env SEMTSDF_MARCH_LPT=0/1 overrides (A/B)
-#endif
-
 namespace {
 
 thread_local std::string g_err;
@@ -164,13 +154,9 @@ struct semtsdf_vol {
 namespace {
 
 // Flags of the events that order this device's own streams (prepass, map update, frame sets):
-// no timing and, by default, a device-scope release (the consumers are kernels of the same
-// device, never the host).  SEMTSDF_EVENT_FLAGS=0 selects the default system-scope release.
-unsigned order_event_flags() {
-    static const char* e = getenv("SEMTSDF_EVENT_FLAGS");
-    static const int mode = e ? atoi(e) : SEMTSDF_EVENT_FLAGS_DEFAULT;
-    return hipEventDisableTiming | (mode == 1 ? hipEventReleaseToDevice : 0u) | (mode == 2 ? hipEventDisableSystemFence : 0u);
-}
+// no timing and no system-scope fence at the record (the consumers are kernels of the same
+// device, never the host).
+unsigned order_event_flags() { return hipEventDisableTiming | hipEventDisableSystemFence; }
 
 size_t npx(const semtsdf_vol* v) { return (size_t)v->p.width * (size_t)v->p.height; }
 
@@ -363,11 +349,9 @@ int ensure_prep_stream(semtsdf_vol* v) {
 // handle's own stream and the set's last reader ran on it too, inputs_ready follows that reader
 // and the prepass needs no frame-set event; on any other stream (a caller's, whose lifetime the
 // handle does not control) the set's event is recorded after every integrate and waited for.
-// pre_done: the frame's depth pyramid is already in the next frame set (computed in the fused
-// march's launch, raw labels): only the cull runs, on s.
 int integrate_impl(semtsdf_vol* v, const uint16_t* depth_d, const uint8_t* rgb_d, const uint8_t* mask_d,
                    const int32_t* cls_d, const float E[16], hipStream_t s, bool async = false,
-                   hipEvent_t inputs_ready = nullptr, bool inputs_on_s = false, bool pre_done = false) {
+                   hipEvent_t inputs_ready = nullptr, bool inputs_on_s = false) {
     if (!E) return fail(SEMTSDF_ERR_INVALID, "E is NULL");
     if (!depth_d || !rgb_d) return fail(SEMTSDF_ERR_INVALID, "depth/rgb is NULL");
     if ((v->p.flags & SEMTSDF_F_SEMANTIC) && !mask_d) return fail(SEMTSDF_ERR_INVALID, "semantic volume needs a mask");
@@ -428,11 +412,11 @@ int integrate_impl(semtsdf_vol* v, const uint16_t* depth_d, const uint8_t* rgb_d
     // that prepass follows the association on s
     // asynchronous with a pending relabel: the prepass writes the frame's raw labels beside
     // the association, and the relabel of the mask and of the records' label bytes follows
-    // the decision on s (k_relabel_records)
+    // the decision on s (by the integrate itself, below)
     // the pending table stays set until the launch consuming it is queued: an error before
     // that leaves it for relabel_unconsumed (the decision already advanced num_objs)
     const uint8_t* lut = mask_d ? v->pending_lut : nullptr;
-    const bool relabel_after = (async || pre_done) && lut;
+    const bool relabel_after = async && lut;
     if (async)
         if (int rc = ensure_prep_stream(v)) return rc;
     hipStream_t ps = s;
@@ -454,9 +438,8 @@ int integrate_impl(semtsdf_vol* v, const uint16_t* depth_d, const uint8_t* rgb_d
     v->next_set = (v->next_set + 1) % kFrameSets;
     EventPair epp;
     timing_begin(v, v->ev_prep, ps, &epp);
-    if (!pre_done)
-        HIPC(launch_depth_pyramid(depth_d, rgb_d, const_cast<uint8_t*>(mask_d), v->p.width, v->p.height,
-                                  v->p.depth_scale, F.pyr, F.list_count, ps, relabel_after ? nullptr : lut));
+    HIPC(launch_depth_pyramid(depth_d, rgb_d, const_cast<uint8_t*>(mask_d), v->p.width, v->p.height,
+                              v->p.depth_scale, F.pyr, F.list_count, ps, relabel_after ? nullptr : lut));
     if (lut && !relabel_after) v->pending_lut = nullptr;  // consumed by the prepass
     HIPC(launch_cull(a, ps));
     HIPC(launch_compact_lists(a, ps));
@@ -468,12 +451,8 @@ int integrate_impl(semtsdf_vol* v, const uint16_t* depth_d, const uint8_t* rgb_d
     }
     // the relabel of a frame whose prepass ran beside its association: by the integrate
     // itself (records mapped as they are read, the mask at the kernel's end; one launch and the
-    // stream gap in front of it fewer) or, with SEMTSDF_RELABEL_KERNEL=1, by k_relabel_records
-    static const bool relabel_kernel = getenv("SEMTSDF_RELABEL_KERNEL") && atoi(getenv("SEMTSDF_RELABEL_KERNEL"));
-    if (relabel_after && relabel_kernel) {
-        HIPC(launch_relabel_records(const_cast<uint8_t*>(mask_d), v->p.width, v->p.height, F.pyr, v->decision_d, s));
-        v->pending_lut = nullptr;
-    } else if (relabel_after) {
+    // stream gap in front of it fewer than with a relabel kernel)
+    if (relabel_after) {
         a.lut = &v->decision_d->lut[0];
         a.relabel_mask = const_cast<uint8_t*>(mask_d);
     }
@@ -569,12 +548,7 @@ int ensure_bmin(semtsdf_vol* v, hipStream_t s) {
     if (int rc = order_after_map(v, s)) return rc;
     if (!v->bmin_dirty && !v->bmin_stale) return SEMTSDF_OK;
     // stale (reset/upload): every brick; dirty (integrate): the bricks the cull marked
-    // the octant maps by the global-memory passes (default) or the LDS line passes (same maps,
-    // measured no faster: profiles/r04/ab_map_passes_pipeline.txt); env SEMTSDF_MAP_GLOBAL=0/1
-    // chooses, instrumentation bit 3 takes the other one (tests)
-    static const char* mg = getenv("SEMTSDF_MAP_GLOBAL");
-    static const bool global_default = mg ? atoi(mg) != 0 : true;
-    HIPC(launch_brick_min(v->g, v->b, v->bmin_stale, s, global_default != ((v->instr & 8) != 0)));
+    HIPC(launch_brick_min(v->g, v->b, v->bmin_stale, s));
     v->map_stream = s;
     v->map_set = true;
     v->bmin_ev_set = false;
@@ -624,12 +598,8 @@ DecideArgs decide_args(semtsdf_vol* v, const uint8_t* mask_d, AssocPixels px, bo
 // integrate's prepass (v->pending_lut), saving a launch.
 // view (optional): a render of the same volume state launched together with the march
 // (k_march_fused); its arguments were validated by the caller.
-// pre_depth/pre_rgb (with a view): the frame's mask statistics and its prepass tiles (depth
-// pyramid into the next frame set, raw labels) run as the first blocks of the fused launch; the
-// caller's integrate then skips the pyramid (integrate_impl pre_done).
 int associate_impl(semtsdf_vol* v, uint8_t* mask_d, const float E[16], hipStream_t s, bool want_decision,
-                   bool defer_relabel = false, const RenderArgs* view = nullptr, const uint16_t* pre_depth = nullptr,
-                   const uint8_t* pre_rgb = nullptr) {
+                   bool defer_relabel = false, const RenderArgs* view = nullptr) {
     if (v->p.z_nshards != 1) return fail(SEMTSDF_ERR_UNSUPPORTED, "association on a Z-sharded handle is not supported yet");
     if (!(v->p.flags & SEMTSDF_F_SEMANTIC)) return fail(SEMTSDF_ERR_STATE, "association needs a SEMANTIC volume");
     if (v->n_obs == 0) return fail(SEMTSDF_ERR_STATE, "association needs n_obs > 0 (tsdf.cu:426)");
@@ -637,8 +607,7 @@ int associate_impl(semtsdf_vol* v, uint8_t* mask_d, const float E[16], hipStream
     timing_begin(v, v->ev_assoc, s, &ep);
     if (int rc = ensure_bmin(v, s)) return rc;
     if (int rc = tables_ready(v, s)) return rc;
-    const bool fold = view && pre_depth && pre_rgb;
-    if (!fold) HIPC(launch_mask_stats(mask_d, (int)npx(v), v->tables_d, s));
+    HIPC(launch_mask_stats(mask_d, (int)npx(v), v->tables_d, s));
     AssocArgs a{};
     a.g = v->g;
     a.b = v->b;
@@ -651,51 +620,26 @@ int associate_impl(semtsdf_vol* v, uint8_t* mask_d, const float E[16], hipStream
     a.mask = mask_d;
     a.tables = v->tables_d;
     a.px = v->px;
-    {
-        static const char* dbg = getenv("SEMTSDF_DEBUG_ASSOC");  // timing probes only
-        a.debug = dbg ? atoi(dbg) : 0;
-    }
     int order_n = 0;  // the decision orders the fused march's next launch (largest tiles first)
     if (view) {
         RenderArgs r = *view;
         r.b = v->b;  // the map buffers as ensure_bmin left them
-        static const char* lpt = getenv("SEMTSDF_MARCH_LPT");
-        if (lpt ? atoi(lpt) != 0 : SEMTSDF_MARCH_LPT_DEFAULT) {
-            const int n = ((a.width + 15) / 16) * ((a.height + 15) / 16) + ((r.width + 15) / 16) * ((r.height + 15) / 16);
-            if (n <= 8192 && n > v->tile_cap) {  // tile_order sorts up to 8192 tiles (256 x kTileOrderPer)
-                for (unsigned** q : {&v->tile_cost_d, &v->tile_perm_d})
-                    if (*q) { (void)hipFree(*q); v->device_bytes -= (size_t)v->tile_cap * sizeof(unsigned); *q = nullptr; }
-                v->tile_cap = 0;
-                v->tile_n = 0;
-                if (int rc = dev_alloc(v, (void**)&v->tile_cost_d, (size_t)n * sizeof(unsigned))) return rc;
-                if (int rc = dev_alloc(v, (void**)&v->tile_perm_d, (size_t)n * sizeof(unsigned))) return rc;
-                v->tile_cap = n;
-            }
-            if (n <= 8192) {
-                a.tile_cost = v->tile_cost_d;
-                a.tile_perm = v->tile_n == n ? v->tile_perm_d : nullptr;  // sizes changed: identity
-                order_n = n;
-            }
+        const int n = ((a.width + 15) / 16) * ((a.height + 15) / 16) + ((r.width + 15) / 16) * ((r.height + 15) / 16);
+        if (n <= 8192 && n > v->tile_cap) {  // tile_order sorts up to 8192 tiles (256 x kTileOrderPer)
+            for (unsigned** q : {&v->tile_cost_d, &v->tile_perm_d})
+                if (*q) { (void)hipFree(*q); v->device_bytes -= (size_t)v->tile_cap * sizeof(unsigned); *q = nullptr; }
+            v->tile_cap = 0;
+            v->tile_n = 0;
+            if (int rc = dev_alloc(v, (void**)&v->tile_cost_d, (size_t)n * sizeof(unsigned))) return rc;
+            if (int rc = dev_alloc(v, (void**)&v->tile_perm_d, (size_t)n * sizeof(unsigned))) return rc;
+            v->tile_cap = n;
         }
-        FramePre pre{};
-        if (fold) {
-            const DepthPyramid& pyr = v->fs[v->next_set].pyr;  // the set the caller's integrate uses next
-            pre.mask = mask_d;
-            pre.npx = (int)npx(v);
-            pre.T = v->tables_d;
-            pre.nms = std::min(64, (pre.npx + 255) / 256);
-            pre.depth = pre_depth;
-            pre.rgb = pre_rgb;
-            pre.pmask = mask_d;
-            pre.w = v->p.width;
-            pre.h = v->p.height;
-            pre.scale = v->p.depth_scale;
-            pre.vec = depth_pyramid_vec(pre_depth, pre_rgb, mask_d, v->p.width, pyr);
-            pre.pyr = pyr;
-            pre.list_count = v->fs[v->next_set].list_count;
-            pre.npy = pyr.w1 * pyr.h1;
+        if (n <= 8192) {
+            a.tile_cost = v->tile_cost_d;
+            a.tile_perm = v->tile_n == n ? v->tile_perm_d : nullptr;  // sizes changed: identity
+            order_n = n;
         }
-        HIPC(launch_march_fused(a, r, pre, s));
+        HIPC(launch_march_fused(a, r, s));
         v->n_render++;
     } else {
         HIPC(launch_assoc_march(a, s));
@@ -1409,9 +1353,6 @@ int semtsdf_parse_frame_dev(semtsdf_vol* v, const uint16_t* depth_d, const uint8
     return semtsdf_parse_frame_dev_after(v, depth_d, rgb_d, mask_d, E, nullptr, stream);
 }
 
-#ifndef SEMTSDF_OVERLAP_PREP
-#define SEMTSDF_OVERLAP_PREP 1  // parse_frame_dev paths: the frame prepass on the prep stream beside the march
-#endif
 static int launch_view(semtsdf_vol* v, const RenderArgs& view, hipStream_t s);
 static int render_args(semtsdf_vol* v, const float s2w[16], const float c[3], int mode, uint8_t* out_bgr_d,
                        float* out_t_d, RenderArgs& a);
@@ -1430,21 +1371,14 @@ static int parse_frame_dev_impl(semtsdf_vol* v, const uint16_t* depth_d, const u
     // beside the march (it reads only the frame's inputs), from the work queued so far on s
     // (the mask statistics stay on s: on the prep stream they slowed the fused view + march
     // launch, 2.45 -> 2.20 k frames/s same-box, profiles/r03/s2/ab_pipeline_mask_stats.txt)
-    // fused view with the frame's mask statistics and depth pyramid folded into the march's
-    // launch (SEMTSDF_FRAME_FOLD): everything on s, no prep-stream events
-    static const char* ff_env = getenv("SEMTSDF_FRAME_FOLD");
-    static const bool ff_on = ff_env ? atoi(ff_env) != 0 : SEMTSDF_FRAME_FOLD_DEFAULT;
-    const bool fold = (ff_on || (v->instr & 16)) && fused && !integrate_after_event;
-    const bool overlap_prep = !fold && SEMTSDF_OVERLAP_PREP && sem && v->n_obs > 0 && !integrate_after_event;
+    const bool overlap_prep = sem && v->n_obs > 0 && !integrate_after_event;
     if (overlap_prep) {
         if (!v->in_ev) HIPC(hipEventCreateWithFlags(&v->in_ev, order_event_flags()));
         HIPC(hipEventRecord(v->in_ev, s));
     }
     if (sem) {
         if (v->n_obs > 0) {
-            int rc = associate_impl(v, mask_d, E, s, false, true, fused ? view : nullptr, fold ? depth_d : nullptr,
-                                    fold ? rgb_d : nullptr);
-            if (rc) return rc;
+            if (int rc = associate_impl(v, mask_d, E, s, false, true, fused ? view : nullptr)) return rc;
         } else {
             if (int rc = tables_ready(v, s)) return rc;
             HIPC(launch_mask_stats(mask_d, (int)npx(v), v->tables_d, s));
@@ -1455,7 +1389,7 @@ static int parse_frame_dev_impl(semtsdf_vol* v, const uint16_t* depth_d, const u
     // other streams (a live render) finish first; the association above, a read, may overlap them
     if (integrate_after_event) HIPC(hipStreamWaitEvent(s, (hipEvent_t)integrate_after_event, 0));
     int rc = integrate_impl(v, depth_d, rgb_d, sem ? mask_d : nullptr, nullptr, E, s, overlap_prep,
-                            overlap_prep ? v->in_ev : nullptr, overlap_prep, fold);
+                            overlap_prep ? v->in_ev : nullptr, overlap_prep);
     if (rc) return relabel_unconsumed(v, mask_d, s, rc);
     v->n_obs++;
     // the next frame's association (and a live view) march this state: refresh the

@@ -256,7 +256,6 @@ struct AssocArgs {
     float* probs_out;       // optional debug [H*W*32]
     uint8_t* box_out;       // optional debug [H*W*32]
     AssocPixels px;         // per-pixel data for the decision's exact path (bits == nullptr: none)
-    int debug;              // timing probes (SEMTSDF_DEBUG_ASSOC): 1 no accumulation, 2 no march
     // k_march_fused launch order (heaviest tiles of the previous frame first): the kernel
     // writes each tile's duration to tile_cost[tile] and takes block b's tile from tile_perm[b]
     // (nullptr: identity); the next decision computes the next order (DecideArgs::tile_*)
@@ -325,9 +324,7 @@ hipError_t launch_masks_to_labels(const uint8_t* masks, int npx, int n, int min_
                                   hipStream_t s);
 size_t mask_scratch_bytes();
 size_t mask_scratch_kept_offset();
-// global_passes: the octant maps by k_brick_dilate + k_brick_oct_axis, else by the LDS line
-// passes (k_brick_oct_lds); both give the same maps.
-hipError_t launch_brick_min(const VolGeom& g, const VolBufs& b, bool all, hipStream_t s, bool global_passes = false);
+hipError_t launch_brick_min(const VolGeom& g, const VolBufs& b, bool all, hipStream_t s);
 hipError_t launch_fill_volume(const VolGeom& g, const VolBufs& b, uint32_t flags, hipStream_t s);
 hipError_t launch_depth_pyramid(const uint16_t* depth, const uint8_t* rgb, uint8_t* mask, int w, int h,
                                 float scale, const DepthPyramid& p, unsigned* list_count, hipStream_t s,
@@ -357,28 +354,8 @@ hipError_t launch_assoc_from_probs(const float* probs, const uint8_t* box, const
 hipError_t launch_libm_eval(int fn, const float* x, float* y, size_t n, hipStream_t s);
 hipError_t launch_first_frame_objs(const AssocTables* t, int* num_objs_dev, hipStream_t s);
 hipError_t launch_relabel(uint8_t* mask, int npx, const AssocDecision* d, hipStream_t s);
-hipError_t launch_relabel_records(uint8_t* mask, int w, int h, const DepthPyramid& p, const AssocDecision* d, hipStream_t s);
 hipError_t launch_render(const RenderArgs& a, hipStream_t s);
-// Work of the frame folded into the fused march's launch (blocks before the march tiles): nms
-// blocks of mask statistics (k_mask_stats) and npy = pyr.w1 * pyr.h1 prepass tiles
-// (k_depth_pyramid, raw labels); nms = npy = 0: none.
-struct FramePre {
-    const uint8_t* mask;
-    int npx;
-    AssocTables* T;
-    int nms;
-    const uint16_t* depth;
-    const uint8_t* rgb;
-    uint8_t* pmask;
-    int w, h;
-    float scale;
-    int vec;
-    DepthPyramid pyr;
-    unsigned* list_count;
-    int npy;
-};
-hipError_t launch_march_fused(const AssocArgs& aa, const RenderArgs& ra, const FramePre& pre, hipStream_t s);
-int depth_pyramid_vec(const uint16_t* depth, const uint8_t* rgb, const uint8_t* mask, int w, const DepthPyramid& p);
+hipError_t launch_march_fused(const AssocArgs& aa, const RenderArgs& ra, hipStream_t s);
 hipError_t launch_copy_host(const void* src, void* dst, size_t n16, hipStream_t s);
 // chunk [v0, v0+nv) of the bin-major histogram <-> voxel-major [nv][32] staging buffer
 hipError_t launch_hist_chunk_to_vm(const uint32_t* bm, uint32_t* vm, const VolGeom& g, uint64_t v0, uint64_t nv,

@@ -369,110 +369,6 @@ __global__ __launch_bounds__(256) void k_brick_oct_axis(VolGeom g, const uint64_
     }
 }
 
-// The octant maps through LDS, one launch per axis, with the dilation folded in.  A workgroup
-// holds L whole lines of n bricks along the pass's axis (lines adjacent in memory, so loads and
-// stores coalesce); the neighbour scans then read LDS instead of re-reading the map.  The
-// dilation k_brick_dilate applies before the passes (min over b + {0,1}^3, here per octant byte:
-// skippable iff every brick of the 2x2x2 box is) is separable into a min with the +1 neighbour
-// along each axis, and each of those commutes with the passes along the other axes (a min over
-// a shift along one axis, a min-max over another: max distributes over min), so the pass along
-// axis A first takes the min with the +1 neighbour along A and then scans: the three passes give
-// exactly the maps of k_brick_dilate + k_brick_oct_axis x3.  The first pass reads the plain map
-// (FIRST: skippable = plain >= thr); bmin (the float dilated map, read only by volumes without
-// octant maps) is not kept on this path.  Dynamic LDS: 2 n L words.
-template <int AXIS, bool FIRST>
-__global__ __launch_bounds__(256) void k_brick_oct_lds(VolGeom g, const void* __restrict__ in_, uint64_t* __restrict__ out,
-                                                       uint8_t* __restrict__ sym, uint32_t* __restrict__ dlist, int L) {
-    extern __shared__ uint64_t s_map[];  // raw [n][L], then dilated [n][L]
-    const int n = AXIS == 0 ? g.nbx : AXIS == 1 ? g.nby : g.nbz;
-    const unsigned S = AXIS == 0 ? (unsigned)g.nby * g.nbz : AXIS == 1 ? (unsigned)g.nbz : 1u;
-    const unsigned nlines = AXIS == 0 ? (unsigned)g.nby * g.nbz : AXIS == 1 ? (unsigned)g.nbx * g.nbz : (unsigned)g.nbx * g.nby;
-    const unsigned q0 = blockIdx.x * (unsigned)L;
-    const int ne = n * L;
-    uint64_t* raw = s_map;
-    uint64_t* dil = s_map + ne;
-    if (FIRST && dlist && blockIdx.x == 0 && threadIdx.x == 0) dlist[0] = 0u;  // k_brick_plain consumed the dirty list
-    auto base = [&](unsigned q) -> unsigned {  // first brick of line q
-        if (AXIS == 0) return q;                                                // (by, bz)
-        if (AXIS == 1) return (q / (unsigned)g.nbz) * (unsigned)g.nby * g.nbz + q % (unsigned)g.nbz;  // (bx, bz)
-        return q * (unsigned)g.nbz;                                             // (bx, by)
-    };
-    // element e <-> (k along the line, l = line): along z the lines are contiguous (k fastest),
-    // else adjacent lines are adjacent in memory (l fastest)
-    auto split = [&](int e, int& k, int& l) {
-        if (AXIS == 2) { k = e % n; l = e / n; } else { k = e / L; l = e - (e / L) * L; }
-    };
-    const float thr = skip_threshold(g);
-    for (int e = (int)threadIdx.x; e < ne; e += 256) {
-        int k, l;
-        split(e, k, l);
-        const unsigned q = q0 + (unsigned)l;
-        uint64_t w = 0ull;
-        if (q < nlines) {
-            const unsigned br = base(q) + (unsigned)k * S;
-            if (FIRST) w = reinterpret_cast<const float*>(in_)[br] >= thr ? (uint64_t)kBrickDistCap * 0x0101010101010101ull : 0ull;
-            else w = reinterpret_cast<const uint64_t*>(in_)[br];
-        }
-        raw[k * L + l] = w;
-    }
-    __syncthreads();
-    for (int e = (int)threadIdx.x; e < ne; e += 256) {  // the +1 neighbour along the axis (inside the volume)
-        int k, l;
-        split(e, k, l);
-        uint64_t w = raw[k * L + l];
-        if (k + 1 < n) {
-            u16x2 a[4], b[4];
-            oct_unpack<0>(w, w, a);
-            const uint64_t v = raw[(k + 1) * L + l];
-            oct_unpack<0>(v, v, b);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] = __builtin_elementwise_min(a[j], b[j]);
-            const uint32_t lo = (uint32_t)a[0].x | ((uint32_t)a[1].x << 8) | ((uint32_t)a[0].y << 16) | ((uint32_t)a[1].y << 24);
-            const uint32_t hi = (uint32_t)a[2].x | ((uint32_t)a[3].x << 8) | ((uint32_t)a[2].y << 16) | ((uint32_t)a[3].y << 24);
-            w = (uint64_t)lo | ((uint64_t)hi << 32);
-        }
-        dil[k * L + l] = w;
-    }
-    __syncthreads();
-    auto hmax = [](const u16x2* x) {
-        const u16x2 m = __builtin_elementwise_max(__builtin_elementwise_max(x[0], x[1]), __builtin_elementwise_max(x[2], x[3]));
-        return (int)max(m.x, m.y);
-    };
-    for (int e = (int)threadIdx.x; e < ne; e += 256) {
-        int k, l;
-        split(e, k, l);
-        const unsigned q = q0 + (unsigned)l;
-        const uint64_t v = dil[k * L + l];
-        u16x2 d[4];
-        oct_unpack<0>(v, v, d);
-        int dmax = hmax(d);
-        for (int k0 = 1; k0 < kBrickDistCap && k0 < dmax; k0 += 4) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int kk = k0 + i;
-                const uint64_t wp = (kk < kBrickDistCap && k + kk < n) ? dil[(k + kk) * L + l] : ~0ull;
-                const uint64_t wn = (kk < kBrickDistCap && k - kk >= 0) ? dil[(k - kk) * L + l] : ~0ull;
-                u16x2 w[4];
-                oct_unpack<AXIS>(wp, wn, w);
-                const u16x2 kv = {(unsigned short)kk, (unsigned short)kk};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) d[j] = __builtin_elementwise_min(d[j], __builtin_elementwise_max(w[j], kv));
-            }
-            dmax = hmax(d);
-        }
-        if (q < nlines) {
-            const unsigned br = base(q) + (unsigned)k * S;
-            const uint32_t lo = (uint32_t)d[0].x | ((uint32_t)d[1].x << 8) | ((uint32_t)d[0].y << 16) | ((uint32_t)d[1].y << 24);
-            const uint32_t hi = (uint32_t)d[2].x | ((uint32_t)d[3].x << 8) | ((uint32_t)d[2].y << 16) | ((uint32_t)d[3].y << 24);
-            out[br] = (uint64_t)lo | ((uint64_t)hi << 32);
-            if (sym) {
-                const u16x2 m = __builtin_elementwise_min(__builtin_elementwise_min(d[0], d[1]), __builtin_elementwise_min(d[2], d[3]));
-                sym[br] = (uint8_t)min(min((int)m.x, (int)m.y), kBrickDistCap);
-            }
-        }
-    }
-}
-
 // Super-brick level: sbmin[s] = min of bmin over the (up to) 8^3 bricks of super-brick s,
 // so it bounds every trilinear sample based in its 64^3 voxels.  One wave per super-brick.
 __global__ __launch_bounds__(256) void k_brick_super(VolGeom g, const float* __restrict__ bmin, float* __restrict__ sbmin) {
@@ -490,10 +386,7 @@ __global__ __launch_bounds__(256) void k_brick_super(VolGeom g, const float* __r
     if (lane == 0) sbmin[sb] = m;
 }
 
-// Lines per workgroup of k_brick_oct_lds for lines of n bricks (0: too long, global passes).
-static int oct_lds_lines(int n) { return n > 1024 ? 0 : n >= 512 ? 1 : 512 / n; }
-
-hipError_t launch_brick_min(const VolGeom& g, const VolBufs& b, bool all, hipStream_t s, bool global_passes) {
+hipError_t launch_brick_min(const VolGeom& g, const VolBufs& b, bool all, hipStream_t s) {
     const unsigned nb = (unsigned)g.nbx * g.nby * g.nbz;
     if (nb == 0) return hipSuccess;
     const unsigned nq = (unsigned)g.nbx * g.nby * (unsigned)((g.nbz + 3) / 4);
@@ -501,17 +394,6 @@ hipError_t launch_brick_min(const VolGeom& g, const VolBufs& b, bool all, hipStr
     hipLaunchKernelGGL(k_brick_plain, dim3((nw + 3) / 4), dim3(256), 0, s, g, b.sdf, b.bplain, b.bdirty, b.dlist,
                        all ? 1 : 0);
     const bool dist = b.bdist && b.boct && b.botmp;
-    const int Lx = oct_lds_lines(g.nbx), Ly = oct_lds_lines(g.nby), Lz = oct_lds_lines(g.nbz);
-    if (dist && !global_passes && Lx && Ly && Lz) {  // plain -> x -> boct -> y -> botmp -> z -> boct (+ bdist)
-        const unsigned lx = (unsigned)g.nby * g.nbz, ly = (unsigned)g.nbx * g.nbz, lz = (unsigned)g.nbx * g.nby;
-        hipLaunchKernelGGL((k_brick_oct_lds<0, true>), dim3((lx + Lx - 1) / Lx), dim3(256), 2 * g.nbx * Lx * 8, s, g,
-                           (const void*)b.bplain, b.boct, (uint8_t*)nullptr, b.dlist, Lx);
-        hipLaunchKernelGGL((k_brick_oct_lds<1, false>), dim3((ly + Ly - 1) / Ly), dim3(256), 2 * g.nby * Ly * 8, s, g,
-                           (const void*)b.boct, b.botmp, (uint8_t*)nullptr, (uint32_t*)nullptr, Ly);
-        hipLaunchKernelGGL((k_brick_oct_lds<2, false>), dim3((lz + Lz - 1) / Lz), dim3(256), 2 * g.nbz * Lz * 8, s, g,
-                           (const void*)b.botmp, b.boct, b.bdist, (uint32_t*)nullptr, Lz);
-        return hipGetLastError();
-    }
     hipLaunchKernelGGL(k_brick_dilate, dim3((nb + 255) / 256), dim3(256), 0, s, g, b.bplain, b.bmin,
                        dist ? b.botmp : nullptr, b.dlist);
     if (dist) {  // d0 in botmp -> x -> boct -> y -> botmp -> z -> boct (+ bdist)
@@ -543,8 +425,7 @@ hipError_t launch_fill_volume(const VolGeom& g, const VolBufs& b, uint32_t flags
 // ------------------------------------------------------------------------------------
 // lut (optional): the association's relabel table (k_relabel folded in): labels are mapped
 // through it and the relabelled mask is written back in place.
-// One 32x32-pixel tile (tx, ty) of the prepass, a whole workgroup (k_depth_pyramid, and the
-// prepass blocks of k_march_fused).
+// One 32x32-pixel tile (tx, ty) of the prepass, a whole workgroup (k_depth_pyramid).
 __device__ __forceinline__ void pyramid_tile(const uint16_t* __restrict__ depth, const uint8_t* __restrict__ rgb,
                                              uint8_t* mask, int w, int h, float scale, int vec, const DepthPyramid& p,
                                              unsigned* list_count, const uint8_t* __restrict__ lut, int tx, int ty) {
@@ -652,7 +533,7 @@ __global__ __launch_bounds__(256) void k_depth_pyramid(const uint16_t* __restric
 }
 
 // Whether the prepass may use its vector path (4-pixel rows aligned).
-int depth_pyramid_vec(const uint16_t* depth, const uint8_t* rgb, const uint8_t* mask, int w, const DepthPyramid& p) {
+static int depth_pyramid_vec(const uint16_t* depth, const uint8_t* rgb, const uint8_t* mask, int w, const DepthPyramid& p) {
     return (w % 4 == 0) && ((uintptr_t)depth % 8 == 0) && (!rgb || (uintptr_t)rgb % 4 == 0) &&
            (!mask || (uintptr_t)mask % 4 == 0);
 }
@@ -2608,8 +2489,7 @@ __device__ __forceinline__ void ray_render(const MarchCamera& c, int x, int y, f
 // mask statistics: max label and first pixel of every label (for the relabel order of
 // tsdf.cu:371-389 and num_objs of tsdf.cu:463-468)
 // ------------------------------------------------------------------------------------
-// Block `blk` of `nblk` of the frame's mask statistics (k_mask_stats, and the mask-statistics
-// blocks of k_march_fused).
+// Block `blk` of `nblk` of the frame's mask statistics (k_mask_stats).
 __device__ __forceinline__ void mask_stats_block(const uint8_t* __restrict__ mask, int npx, AssocTables* t, int blk,
                                                  int nblk) {
     __shared__ unsigned s_first[256];
@@ -2815,15 +2695,16 @@ __device__ __forceinline__ void assoc_tile(const AssocArgs& a, AssocLds& s, int 
     if (x < a.width && y < a.height) {
         float ox, oy, oz, dx, dy, dz, t;
         ray_assoc(a.cam, x, y, &ox, &oy, &oz, &dx, &dy, &dz);
+        const int px = y * a.width + x;
+        const unsigned lab = a.mask[px];  // read before the march: the mask pointer is not kept across it
         float p[kMaxObjects];
 #pragma unroll
         for (int k = 0; k < kMaxObjects; ++k) p[k] = 0.0f;
         unsigned bins = 0;
-        if (a.debug != 2 && march_ray<OCT>(a.g, a.b, ox, oy, oz, dx, dy, dz, &t)) {
+        if (march_ray<OCT>(a.g, a.b, ox, oy, oz, dx, dy, dz, &t)) {
             const Tri tr = tri_setup<false>(a.g, fmaf(t, dx, ox), fmaf(t, dy, oy), fmaf(t, dz, oz));
             bins = tri_hist(a.g, a.b, tr, p);
         }
-        const int px = y * a.width + x;
         if (a.px.bits && !sparse) assoc_pixel_out(a.px, a.width * a.height, px, p, bins, a.box_thresh);
         if (a.probs_out) {
 #pragma unroll
@@ -2832,13 +2713,10 @@ __device__ __forceinline__ void assoc_tile(const AssocArgs& a, AssocLds& s, int 
                 a.box_out[(size_t)px * kMaxObjects + k] = p[k] > a.box_thresh ? 1 : 0;
             }
         }
-        if (a.debug != 1) {
-            if (sparse)
-                assoc_accumulate_sparse(s, p, bins, a.mask[px], a.n_obs, a.eps, a.box_thresh, F0, a.px,
-                                        a.width * a.height, px);
-            else
-                assoc_accumulate(s, p, a.mask[px], a.n_obs, a.eps, a.box_thresh);
-        }
+        if (sparse)
+            assoc_accumulate_sparse(s, p, bins, lab, a.n_obs, a.eps, a.box_thresh, F0, a.px, a.width * a.height, px);
+        else
+            assoc_accumulate(s, p, lab, a.n_obs, a.eps, a.box_thresh);
     }
     __syncthreads();
     AssocTables* T = a.tables;
@@ -3538,50 +3416,6 @@ hipError_t launch_relabel(uint8_t* mask, int npx, const AssocDecision* d, hipStr
     return hipGetLastError();
 }
 
-// The relabel of a frame whose prepass ran beside its association march (raw labels in the
-// pixel records): the mask in place and the label byte of each pixel record.  One image row
-// per blockIdx.y; four pixels per lane when the rows are 4-byte aligned (one tile row of
-// records).
-__global__ __launch_bounds__(256) void k_relabel_records(uint8_t* __restrict__ mask, int w, int h, DepthPyramid p,
-                                                         const AssocDecision* __restrict__ d) {
-    __shared__ unsigned char s_lut[256];
-    s_lut[threadIdx.x] = d->lut[threadIdx.x];
-    __syncthreads();
-    const bool vec = ((uintptr_t)mask & 3u) == 0 && (w & 3) == 0;
-    for (int y = blockIdx.y; y < h; y += gridDim.y) {
-        uint8_t* row = mask + (size_t)y * w;
-        if (vec) {
-            for (int x4 = blockIdx.x * blockDim.x + threadIdx.x; x4 < (w >> 2); x4 += gridDim.x * blockDim.x) {
-                const unsigned m4 = reinterpret_cast<const unsigned*>(row)[x4];
-                unsigned o4 = 0;
-                uint2* r = p.px + rec_index(p, (unsigned)(4 * x4), (unsigned)y);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const unsigned m = s_lut[(m4 >> (8 * j)) & 0xFFu];
-                    o4 |= m << (8 * j);
-                    r[4 * j].y = (r[4 * j].y & 0x00FFFFFFu) | (m << 24);  // a tile is column-major
-                }
-                reinterpret_cast<unsigned*>(row)[x4] = o4;
-            }
-        } else {
-            for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < w; x += gridDim.x * blockDim.x) {
-                const unsigned m = s_lut[row[x]];
-                row[x] = (uint8_t)m;
-                uint2& r = p.px[rec_index(p, (unsigned)x, (unsigned)y)];
-                r.y = (r.y & 0x00FFFFFFu) | (m << 24);
-            }
-        }
-    }
-}
-
-hipError_t launch_relabel_records(uint8_t* mask, int w, int h, const DepthPyramid& p, const AssocDecision* d,
-                                  hipStream_t s) {
-    const int bx = ((w + 3) / 4 + 255) / 256;
-    const int by = h < 512 ? (h > 0 ? h : 1) : 512;
-    hipLaunchKernelGGL(k_relabel_records, dim3(bx, by), dim3(256), 0, s, mask, w, h, p, d);
-    return hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------
 // render raycast (show_tsdf_kernel viewer.cu:17-86; colour mode tsdf_render.frag:125-131)
 // ------------------------------------------------------------------------------------
@@ -3681,25 +3515,10 @@ template <bool OCT>
 #define SEMTSDF_FUSED_WPE 4  // 4 waves per SIMD: at most 128 VGPRs (the association's per-pixel output put it at 131)
 #endif
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEMTSDF_FUSED_WPE))) void k_march_fused(
-    AssocArgs aa, RenderArgs ra, FramePre pre, int na, int nr) {
+    AssocArgs aa, RenderArgs ra, int na, int nr) {
     __shared__ AssocLds s;
-    // the frame's mask statistics and prepass tiles first (FramePre: they read only the frame's
-    // inputs; the marches read the volume)
-    const int npre = pre.nms + pre.npy;
-    if ((int)blockIdx.x < npre) {
-        const int pb = (int)blockIdx.x;
-        if (pb < pre.nms) {
-            mask_stats_block(pre.mask, pre.npx, pre.T, pb, pre.nms);
-        } else {
-            const int q = pb - pre.nms;
-            pyramid_tile(pre.depth, pre.rgb, pre.pmask, pre.w, pre.h, pre.scale, pre.vec, pre.pyr, pre.list_count,
-                         nullptr, q % pre.pyr.w1, q / pre.pyr.w1);
-        }
-        return;
-    }
-    const unsigned bt = blockIdx.x - (unsigned)npre;
     // launch order: block b takes tile perm[b] (the previous frame's heaviest first)
-    const int b = aa.tile_perm ? (int)__builtin_amdgcn_readfirstlane(aa.tile_perm[bt]) : (int)bt;
+    const int b = aa.tile_perm ? (int)__builtin_amdgcn_readfirstlane(aa.tile_perm[blockIdx.x]) : (int)blockIdx.x;
     const int m = min(na, nr);
     const uint64_t t0 = aa.tile_cost ? __builtin_amdgcn_s_memrealtime() : 0;
     bool assoc;
@@ -3724,14 +3543,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEMTSDF_FUS
     }
 }
 
-hipError_t launch_march_fused(const AssocArgs& aa, const RenderArgs& ra, const FramePre& pre, hipStream_t s) {
+hipError_t launch_march_fused(const AssocArgs& aa, const RenderArgs& ra, hipStream_t s) {
     const int na = ((aa.width + 15) / 16) * ((aa.height + 15) / 16);
     const int nr = ((ra.width + 15) / 16) * ((ra.height + 15) / 16);
-    const int grid = pre.nms + pre.npy + na + nr;
     if (oct_maps(aa.b))
-        hipLaunchKernelGGL(k_march_fused<true>, dim3(grid), dim3(256), 0, s, aa, ra, pre, na, nr);
+        hipLaunchKernelGGL(k_march_fused<true>, dim3(na + nr), dim3(256), 0, s, aa, ra, na, nr);
     else
-        hipLaunchKernelGGL(k_march_fused<false>, dim3(grid), dim3(256), 0, s, aa, ra, pre, na, nr);
+        hipLaunchKernelGGL(k_march_fused<false>, dim3(na + nr), dim3(256), 0, s, aa, ra, na, nr);
     return hipGetLastError();
 }
 

@@ -813,8 +813,6 @@ def test_parse_frame_view_fused_equals_serial(S, stream, D):
                                  L.PLACE_SFM)
         p.flags = L.F_SEMANTIC | L.F_GATE_COLOR
         vol = semtsdf.Volume(p, 0)
-        if fused == "fold":  # the frame's mask statistics and depth pyramid in the march launch
-            vol.set_instrumentation(events=False, frame_fold=True)
         masks = [m.clone() for m in m_in]
         torch.cuda.synchronize()
         views = []
@@ -847,7 +845,7 @@ def test_parse_frame_view_fused_equals_serial(S, stream, D):
 
     (va, ma), sa = run(False)
     assert sum(int(v.count_nonzero()) for v in va[::2]) > 0
-    for variant in (True, "fold", "host"):
+    for variant in (True, "host"):
         (vb, mb), sb = run(variant)
         for x, y in zip(va + ma, vb + mb):
             assert torch.equal(x, y), variant
@@ -858,7 +856,7 @@ def test_parse_frame_view_fused_equals_serial(S, stream, D):
 def test_parse_frame_ragged_image_device_equals_host_and_oracle(S, oracle, stream):
     """A 637 x 479 image (pixel count not a multiple of 4, rows not 4-aligned): the device
     parse path (prepass beside the march, the relabel of mask and pixel records after the
-    decision, k_relabel_records' per-pixel path) equals the host-pointer parse_frame and the
+    decision, by the integrate's per-pixel path) equals the host-pointer parse_frame and the
     C oracle (masks, object counts, every array)."""
     import torch
 
