@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define SEMTSDF_DET_ABI_VERSION 2
+#define SEMTSDF_DET_ABI_VERSION 3
 #define SEMTSDF_DET_ERR_INVALID 1
 #define SEMTSDF_DET_ERR_HIP 2
 #define SEMTSDF_DET_MAX_BOXES 16384
@@ -39,10 +39,24 @@ size_t semtsdf_det_nms_workspace(int n);
 int semtsdf_det_nms(const float* boxes, int n, float iou_threshold, int max_out, int32_t* keep, int32_t* count,
                     void* work, void* stream);
 
+/* The same with groups (ABI 3): the per-class NMS of refine_detections_graph (model.py:736-750) in one
+ * call.  A box is suppressed only by a kept box of its own group; max_out counts the kept boxes of all
+ * groups together, in order.  The boxes keep their own coordinates: shifting each class's boxes apart by
+ * an offset instead rounds the coordinates (class 80: about 7 mantissa bits) and with them the IoU.
+ *   group:  [n] int32, any values; NULL: one group (semtsdf_det_nms is this call with NULL) */
+int semtsdf_det_nms_grouped(const float* boxes, const int32_t* group, int n, float iou_threshold, int max_out,
+                            int32_t* keep, int32_t* count, void* work, void* stream);
+
 /* PyramidROIAlign of mrcnn/model.py:374-452 (ABI 2): rois [n][4] f32 (y1, x1, y2, x2) normalised to the
  * image, each sampled on its own level lvl[r] in 2..5 (the caller's level rule, model.py:406-413), at
  * tf.image.crop_and_resize's pool x pool positions y = y1 (H - 1) + i (y2 - y1) (H - 1) / (pool - 1),
  * bilinearly in f32, 0 outside the map (extrapolation value 0).
+ * The arithmetic, every operation rounded to f32 on its own (no fused multiply-add), hm = (float)(H - 1),
+ * pm = (float)(pool - 1), the same for x with W:
+ *   y = y1 * hm + (float)i * (((y2 - y1) * hm) / pm);  the sample is inside when 0 <= y <= hm (and x)
+ *   y0 = floor(y), yb = min(y0 + 1, H - 1), fy = y - y0
+ *   top = f[y0][x0] * (1 - fx) + f[y0][xb] * fx;  bot = f[yb][x0] * (1 - fx) + f[yb][xb] * fx
+ *   v = top * (1 - fy) + bot * fy, converted once to dtype, round to nearest even
  *   feats:  the four levels P2..P5, each [C][H[k]][W[k]] contiguous (batch 1, NCHW) in dtype
  *   dtype:  0 fp16, 1 bf16 (the maps' and the output's element type)
  *   out:    [n][C][pool][pool] in dtype */

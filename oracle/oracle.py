@@ -379,15 +379,27 @@ def non_max_suppression(boxes, scores, threshold):
     return np.array(pick, dtype=np.int32)
 
 
-def nms_sorted_cpu(boxes, iou_threshold, max_out):
+def nms_sorted_cpu(boxes, iou_threshold, max_out, groups=None):
     """The product's nms_sorted contract (boxes sorted by descending score; keep [max_out] with -1
-    past the count, count [1]) on CPU torch tensors, from non_max_suppression above: for CPU tests of
-    the detector graph."""
+    past the count, count [1]; groups [n]: a box is suppressed only by a kept box of its own group) on
+    CPU torch tensors, from non_max_suppression above: for CPU tests of the detector graph.  With
+    groups, each group's boxes go through non_max_suppression on their own (the reference's per-class
+    form, model.py:736-750) and the kept indices are merged in order."""
     import torch
 
     b = boxes.detach().float().cpu().numpy()
     n = b.shape[0]
-    pick = non_max_suppression(b, -np.arange(n, dtype=np.float64), iou_threshold)[:max_out] if n else np.zeros(0, np.int32)
+    if groups is None:
+        pick = non_max_suppression(b, -np.arange(n, dtype=np.float64), iou_threshold) if n else np.zeros(0, np.int32)
+    else:
+        g = groups.detach().cpu().numpy()
+        assert g.shape == (n,)
+        parts = [np.zeros(0, np.int64)]
+        for v in np.unique(g):
+            ix = np.nonzero(g == v)[0]
+            parts.append(ix[non_max_suppression(b[ix], -np.arange(len(ix), dtype=np.float64), iou_threshold)])
+        pick = np.sort(np.concatenate(parts)).astype(np.int32)
+    pick = pick[:max_out]
     keep = np.full(max(max_out, 1), -1, np.int32)
     keep[:len(pick)] = pick
     return torch.from_numpy(keep[:max_out]), torch.tensor([len(pick)], dtype=torch.int32)

@@ -4,7 +4,9 @@
 //
 // Two kernels.  k_nms_mask: one workgroup per (row block, column block) of 64 x 64 boxes, column
 // blocks at or right of the row block only; lane r owns box i = 64 bi + r and writes one 64-bit word,
-// bit c set when box 64 bj + c comes after i and overlaps it with IoU > threshold.  k_nms_sweep: one
+// bit c set when box 64 bj + c comes after i, belongs to i's group (grouped call: the per-class NMS of
+// refine_detections_graph on the classes' own, unshifted coordinates) and overlaps it with IoU >
+// threshold.  k_nms_sweep: one
 // workgroup walks the row blocks in order.  Inside a block, wave 0 decides its 64 boxes serially from
 // the block's diagonal words (a register per lane, broadcast by readlane: no memory round trip per box);
 // then the 256 threads OR the kept rows' words right of the block into the LDS removed-bitmap (every
@@ -31,29 +33,34 @@ __device__ __forceinline__ float iou(float ay1, float ax1, float ay2, float ax2,
     return inter / uni;
 }
 
-__global__ __launch_bounds__(64) void k_nms_mask(const float4* __restrict__ boxes, int n, float thr, int ncol,
-                                                 unsigned long long* __restrict__ mask) {
+template <bool GROUPED>
+__global__ __launch_bounds__(64) void k_nms_mask(const float4* __restrict__ boxes, const int* __restrict__ group,
+                                                 int n, float thr, int ncol, unsigned long long* __restrict__ mask) {
     const int bi = (int)blockIdx.y, bj = (int)blockIdx.x;
     if (bj < bi) return;  // the sweep reads only the words at or right of a row's own block
     __shared__ float4 cb[kB];
     __shared__ float ca[kB];
+    __shared__ int cg[kB];
     const int t = (int)threadIdx.x;
     const int j0 = bj * kB;
     if (j0 + t < n) {
         const float4 b = boxes[j0 + t];
         cb[t] = b;
         ca[t] = (b.z - b.x) * (b.w - b.y);
+        if (GROUPED) cg[t] = group[j0 + t];
     }
     __syncthreads();
     const int i = bi * kB + t;
     if (i >= n) return;
     const float4 a = boxes[i];
     const float aa = (a.z - a.x) * (a.w - a.y);
+    const int ga = GROUPED ? group[i] : 0;
     const int nc = min(kB, n - j0);
     unsigned long long w = 0;
     for (int c = 0; c < nc; ++c) {
         const int j = j0 + c;
         if (j <= i) continue;
+        if (GROUPED && cg[c] != ga) continue;
         const float4 b = cb[c];
         if (iou(a.x, a.y, a.z, a.w, aa, b.x, b.y, b.z, b.w, ca[c]) > thr) w |= 1ull << c;
     }
@@ -195,21 +202,32 @@ size_t semtsdf_det_nms_workspace(int n) {
     return (size_t)n * ncol * sizeof(unsigned long long);
 }
 
-int semtsdf_det_nms(const float* boxes, int n, float iou_threshold, int max_out, int32_t* keep, int32_t* count,
-                    void* work, void* stream) {
+int semtsdf_det_nms_grouped(const float* boxes, const int32_t* group, int n, float iou_threshold, int max_out,
+                            int32_t* keep, int32_t* count, void* work, void* stream) {
     if (n < 0 || n > SEMTSDF_DET_MAX_BOXES || max_out < 0 || !keep || !count || (n > 0 && (!boxes || !work)))
         return SEMTSDF_DET_ERR_INVALID;
     if (((uintptr_t)boxes & 15u) != 0) return SEMTSDF_DET_ERR_INVALID;  // float4 rows
     hipStream_t s = (hipStream_t)stream;
     const int ncol = (n + kB - 1) / kB;
     if (n > 0) {
-        hipLaunchKernelGGL(k_nms_mask, dim3(ncol, ncol), dim3(kB), 0, s, reinterpret_cast<const float4*>(boxes), n,
-                           iou_threshold, ncol, reinterpret_cast<unsigned long long*>(work));
+        if (group)
+            hipLaunchKernelGGL(k_nms_mask<true>, dim3(ncol, ncol), dim3(kB), 0, s,
+                               reinterpret_cast<const float4*>(boxes), group, n, iou_threshold, ncol,
+                               reinterpret_cast<unsigned long long*>(work));
+        else
+            hipLaunchKernelGGL(k_nms_mask<false>, dim3(ncol, ncol), dim3(kB), 0, s,
+                               reinterpret_cast<const float4*>(boxes), group, n, iou_threshold, ncol,
+                               reinterpret_cast<unsigned long long*>(work));
         if (hipGetLastError() != hipSuccess) return SEMTSDF_DET_ERR_HIP;
     }
     hipLaunchKernelGGL(k_nms_sweep, dim3(1), dim3(256), 0, s, reinterpret_cast<const unsigned long long*>(work), n,
                        ncol, max_out, keep, count);
     return hipGetLastError() == hipSuccess ? 0 : SEMTSDF_DET_ERR_HIP;
+}
+
+int semtsdf_det_nms(const float* boxes, int n, float iou_threshold, int max_out, int32_t* keep, int32_t* count,
+                    void* work, void* stream) {
+    return semtsdf_det_nms_grouped(boxes, nullptr, n, iou_threshold, max_out, keep, count, work, stream);
 }
 
 int semtsdf_det_roi_align(const void* const feats[4], const int H[4], const int W[4], int C, const float* rois,

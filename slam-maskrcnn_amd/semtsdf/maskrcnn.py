@@ -90,6 +90,9 @@ def _det_lib():
         lib.semtsdf_det_nms.restype = C.c_int
         lib.semtsdf_det_nms.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]
+        lib.semtsdf_det_nms_grouped.restype = C.c_int
+        lib.semtsdf_det_nms_grouped.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
         lib.semtsdf_det_roi_align.restype = C.c_int
         lib.semtsdf_det_roi_align.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -98,23 +101,31 @@ def _det_lib():
     return _det
 
 
-def nms_sorted(boxes: torch.Tensor, iou_threshold: float, max_out: int) -> tuple[torch.Tensor, torch.Tensor]:
+def nms_sorted(boxes: torch.Tensor, iou_threshold: float, max_out: int,
+               groups: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
     """Greedy NMS of device boxes [n, 4] (y1, x1, y2, x2) sorted by descending score (the HIP kernels
     of libsemtsdf_det.so): returns (keep [max_out] int32 with -1 past the count, count [1] int32), both
-    on the device, asynchronous on the current stream."""
+    on the device, asynchronous on the current stream.  groups [n] (integers): a box is suppressed only
+    by a kept box of its own group (the per-class NMS in one call); None: one group."""
     if boxes.device.type != "cuda":
         raise RuntimeError("nms_sorted runs on the GPU (libsemtsdf_det.so); no CPU fallback")
     lib = _det_lib()
     b = boxes.to(torch.float32).contiguous()
     n = int(b.shape[0])
+    g = None
+    if groups is not None:
+        if groups.device != b.device or tuple(groups.shape) != (n,):
+            raise RuntimeError("nms_sorted: groups must be [n] on the boxes' device")
+        g = groups.to(torch.int32).contiguous()
     keep = torch.empty(max(max_out, 1), dtype=torch.int32, device=b.device)
     count = torch.empty(1, dtype=torch.int32, device=b.device)
     work = torch.empty(int(lib.semtsdf_det_nms_workspace(n)), dtype=torch.uint8, device=b.device)
-    rc = lib.semtsdf_det_nms(C.c_void_p(b.data_ptr()), n, float(iou_threshold), int(max_out),
-                             C.c_void_p(keep.data_ptr()), C.c_void_p(count.data_ptr()), C.c_void_p(work.data_ptr()),
-                             C.c_void_p(torch.cuda.current_stream(b.device).cuda_stream))
+    rc = lib.semtsdf_det_nms_grouped(C.c_void_p(b.data_ptr()), C.c_void_p(g.data_ptr()) if g is not None else None,
+                                     n, float(iou_threshold), int(max_out), C.c_void_p(keep.data_ptr()),
+                                     C.c_void_p(count.data_ptr()), C.c_void_p(work.data_ptr()),
+                                     C.c_void_p(torch.cuda.current_stream(b.device).cuda_stream))
     if rc:
-        raise RuntimeError(f"semtsdf_det_nms failed ({rc})")
+        raise RuntimeError(f"semtsdf_det_nms_grouped failed ({rc})")
     return keep[:max_out], count
 
 
@@ -377,7 +388,9 @@ class MaskRCNN(nn.Module):
         cfg = self.config
         scores = torch.softmax(logits, dim=1)[:, 1]
         k = min(cfg.PRE_NMS_LIMIT, scores.shape[0])
-        top, ix = torch.topk(scores, k, sorted=True)
+        # tf.nn.top_k takes the lower index first among equal scores (and equal scores are common: the
+        # logits are fp16 or bf16 values); torch.topk leaves their order open, a stable sort does not
+        ix = torch.sort(scores, descending=True, stable=True).indices[:k]
         d = deltas[ix] * self._const("rpn_std", cfg.RPN_BBOX_STD_DEV, deltas.device)
         boxes = clip_boxes(apply_box_deltas(anchors[ix], d), (0.0, 0.0, 1.0, 1.0))
         keep, count = self._nms(boxes, cfg.RPN_NMS_THRESHOLD, cfg.POST_NMS_ROIS_INFERENCE)
@@ -429,7 +442,8 @@ class MaskRCNN(nn.Module):
 
     def detections(self, rois, probs, deltas, window):
         """refine_detections_graph (model.py:689-784): [n, (y1, x1, y2, x2, class_id, score)], the
-        per-class NMS as one NMS over class-offset boxes (boxes of different classes never overlap)."""
+        per-class NMS as one grouped NMS (a box is suppressed only by a kept box of its own class; the
+        boxes keep their own coordinates, an offset per class would round them and the IoU)."""
         cfg = self.config
         score, cls = probs.max(dim=1)
         d = deltas[torch.arange(deltas.shape[0], device=deltas.device), cls] * self._const("bbox_std", cfg.BBOX_STD_DEV,
@@ -438,9 +452,8 @@ class MaskRCNN(nn.Module):
         ok = (cls > 0) & (score >= cfg.DETECTION_MIN_CONFIDENCE) & (rois.abs().sum(1) > 0)
         score_k = torch.where(ok, score, torch.full_like(score, -1.0))
         order = torch.argsort(score_k, descending=True, stable=True)
-        off = refined[order] + (cls[order].float() * 2.0)[:, None]
         n_ok = ok.sum()
-        keep, count = self._nms(off, cfg.DETECTION_NMS_THRESHOLD, cfg.DETECTION_MAX_INSTANCES)
+        keep, count = self._nms(refined[order], cfg.DETECTION_NMS_THRESHOLD, cfg.DETECTION_MAX_INSTANCES, cls[order])
         # boxes past n_ok (not candidates) sort last and are cut by their -1 score below
         k = keep.clamp(min=0).long()
         sel = order[k]
@@ -511,8 +524,11 @@ class MaskRCNN(nn.Module):
         shift = self._const("shift", (wy1, wx1, wy1, wx1), dev)
         scale = self._const("scale", (wy2 - wy1, wx2 - wx1, wy2 - wy1, wx2 - wx1), dev)
         b = (d[:, :4] - shift) / scale
-        px = torch.round(b * self._const("den", (H0 - 1, W0 - 1, H0 - 1, W0 - 1), dev)
-                         + self._const("den_shift", (0, 0, 1, 1), dev)).to(torch.int32)
+        # denorm_boxes (utils.py:886-889) multiplies the f32 boxes by an integer array, so in f64, and
+        # rounds that; the product rounded to f32 first lands on the other side of a half in about 1 of
+        # 80 000 coordinates
+        px = torch.round(b.double() * self._const("den", (H0 - 1, W0 - 1, H0 - 1, W0 - 1), dev).double()
+                         + self._const("den_shift", (0, 0, 1, 1), dev).double()).to(torch.int32)
         cls = d[:, 4].long()
         ok = ((px[:, 2] - px[:, 0]) * (px[:, 3] - px[:, 1]) > 0) & (cls > 0)
         if compact:

@@ -70,7 +70,8 @@ def test_argument_errors_without_a_device():
     # ABI 9: the decision on given inputs, the libm check, the sharded exact path
     rc = lib.semtsdf_filter_overlaps_dev(None, buf, buf, buf, None, None)
     assert rc != 0 and b"NULL" in lib.semtsdf_last_error()
-    rc = lib.semtsdf_libm_eval(2, buf, buf, 16, None)
+    # (fn 2, the device logf, is valid: with a device present it would be launched on these made-up pointers)
+    rc = lib.semtsdf_libm_eval(3, buf, buf, 16, None)
     assert rc != 0 and b"fn" in lib.semtsdf_last_error()
     rc = lib.semtsdf_shard_assoc_pixels(None, buf, buf, None)
     assert rc != 0 and b"NULL" in lib.semtsdf_last_error()
@@ -107,14 +108,28 @@ def test_detector_library_exports_every_symbol():
     with open(os.path.join(ROOT, "include", "semtsdf_det.h")) as f:
         txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     names = sorted(set(re.findall(r"\b(semtsdf_det_[a-z0-9_]+)\s*\(", txt)))
-    assert names == ["semtsdf_det_abi_version", "semtsdf_det_nms", "semtsdf_det_nms_workspace", "semtsdf_det_roi_align"]
+    assert names == ["semtsdf_det_abi_version", "semtsdf_det_nms", "semtsdf_det_nms_grouped",
+                     "semtsdf_det_nms_workspace", "semtsdf_det_roi_align"]
     lib = C.CDLL(os.path.join(ROOT, "slam-maskrcnn_amd", "semtsdf", "libsemtsdf_det.so"))
     for n in names:
         assert hasattr(lib, n), n
-    assert lib.semtsdf_det_abi_version() == 2
+    assert lib.semtsdf_det_abi_version() == 3
     lib.semtsdf_det_nms_workspace.restype = C.c_size_t
     assert lib.semtsdf_det_nms_workspace(6000) == 6000 * 94 * 8
     lib.semtsdf_det_nms.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]
     assert lib.semtsdf_det_nms(None, 16385, 0.5, 10, None, None, None, None) == 1  # too many boxes, NULLs
     assert lib.semtsdf_det_nms(None, -1, 0.5, 10, None, None, None, None) == 1
+    # ABI 3: the grouped call, the same checks (a NULL group is the ungrouped call, not an error)
+    lib.semtsdf_det_nms_grouped.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]
+    buf = C.c_void_p(0x1000)
+    assert lib.semtsdf_det_nms_grouped(None, None, 16385, 0.5, 10, None, None, None, None) == 1
+    assert lib.semtsdf_det_nms_grouped(None, None, -1, 0.5, 10, None, None, None, None) == 1
+    assert lib.semtsdf_det_nms_grouped(buf, buf, 16385, 0.5, 10, buf, buf, buf, None) == 1  # too many boxes
+    assert lib.semtsdf_det_nms_grouped(buf, buf, 64, 0.5, -1, buf, buf, buf, None) == 1  # max_out < 0
+    assert lib.semtsdf_det_nms_grouped(buf, buf, 64, 0.5, 10, None, buf, buf, None) == 1  # no keep
+    assert lib.semtsdf_det_nms_grouped(buf, buf, 64, 0.5, 10, buf, None, buf, None) == 1  # no count
+    assert lib.semtsdf_det_nms_grouped(None, buf, 64, 0.5, 10, buf, buf, buf, None) == 1  # no boxes
+    assert lib.semtsdf_det_nms_grouped(buf, buf, 64, 0.5, 10, buf, buf, None, None) == 1  # no workspace
+    assert lib.semtsdf_det_nms_grouped(C.c_void_p(0x1004), buf, 64, 0.5, 10, buf, buf, buf, None) == 1  # float4 rows
