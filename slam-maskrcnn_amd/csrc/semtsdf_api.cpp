@@ -121,10 +121,10 @@ struct semtsdf_vol {
     int ray_nrec = 1;              // records per pixel of the exchange (nshards: all-gather; 1: all-reduce MIN)
     int ray_next = 0;              // next expected step
     uint32_t n_obs = 0;
-    bool bmin_dirty = false;       // integrated since the last map update: update marked bricks
-    bool bmin_stale = true;        // reset/upload: rebuild the whole map
-    hipEvent_t bmin_ev = nullptr;  // marks the last map update on map_stream (recorded when needed)
-    bool bmin_ev_set = false;      // bmin_ev covers the last map update
+    bool maps_dirty = false;       // integrated since the last map update: update marked bricks
+    bool maps_stale = true;        // reset/upload: rebuild the whole map
+    hipEvent_t maps_ev = nullptr;  // marks the last map update on map_stream (recorded when needed)
+    bool maps_ev_set = false;      // maps_ev covers the last map update
     hipStream_t map_stream = nullptr;
     bool map_set = false;          // a map update has run (on map_stream)
     bool multi_stream = false;     // the volume has been used from more than one stream
@@ -173,7 +173,7 @@ int dev_alloc(semtsdf_vol* v, void** p, size_t bytes) {
 }
 
 void free_all(semtsdf_vol* v) {
-    void* ptrs[] = {v->b.sdf, v->b.wt, v->b.bmin, v->b.bplain, v->b.sbmin, v->b.bdist, v->b.boct, v->b.botmp, v->b.bdirty, v->b.dlist, v->b.sflag, v->b.color, v->b.hist, v->b.hmask, v->b.cls, v->b.cls_cnt, v->depth_d, v->rgb_d,
+    void* ptrs[] = {v->b.sdf, v->b.wt, v->b.bplain, v->b.boct, v->b.botmp, v->b.bdirty, v->b.dlist, v->b.sflag, v->b.color, v->b.hist, v->b.hmask, v->b.cls, v->b.cls_cnt, v->depth_d, v->rgb_d,
                     v->mask_d, v->cls_d, v->tables_d, v->decision_d,
                     v->num_objs_d, v->probs_d, v->box_d, v->palette_d, v->render_d, v->render_t_d,
                     v->counters_d, v->ray_state_d, v->rcp_table_d, v->wtrace_d, v->exact_d, v->px.bits, v->px.p, v->tile_cost_d, v->tile_perm_d, v->rare_d};
@@ -186,7 +186,7 @@ void free_all(semtsdf_vol* v) {
     if (v->decision_h) (void)hipHostFree(v->decision_h);
     for (auto* vec : {&v->ev_integrate, &v->ev_assoc, &v->ev_render, &v->ev_prep})
         for (auto& e : *vec) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    if (v->bmin_ev) (void)hipEventDestroy(v->bmin_ev);
+    if (v->maps_ev) (void)hipEventDestroy(v->maps_ev);
     for (auto& f : v->fs) {
         if (f.prep_done) (void)hipEventDestroy(f.prep_done);
         if (f.set_free) (void)hipEventDestroy(f.set_free);
@@ -197,7 +197,7 @@ void free_all(semtsdf_vol* v) {
 }
 
 int local_planes(const semtsdf_params* p, int* chunk, int* halo);
-int after_bmin(semtsdf_vol* v, hipStream_t s);
+int after_maps(semtsdf_vol* v, hipStream_t s);
 
 int check_params(const semtsdf_params* p) {
     if (!p) return fail(SEMTSDF_ERR_INVALID, "params is NULL");
@@ -457,7 +457,7 @@ int integrate_impl(semtsdf_vol* v, const uint16_t* depth_d, const uint8_t* rgb_d
         a.relabel_mask = const_cast<uint8_t*>(mask_d);
     }
     // the volume's writer: after the last empty-space map update
-    if (int rc = after_bmin(v, s)) return rc;
+    if (int rc = after_maps(v, s)) return rc;
     v->wmax_bound += 1;
     // timing: the integrate kernel's own start/end (events recorded by its dispatch, the
     // duration rocprofv3 reports for the same kernel)
@@ -501,7 +501,7 @@ int integrate_impl(semtsdf_vol* v, const uint16_t* depth_d, const uint8_t* rgb_d
         HIPC(hipEventRecord(F.set_free, s));
         F.free_recorded = true;
     }
-    v->bmin_dirty = true;
+    v->maps_dirty = true;
     v->n_integrate++;
     return SEMTSDF_OK;
 }
@@ -531,12 +531,12 @@ MarchCamera assoc_camera(const semtsdf_vol* v, const float E[16]) {
 int order_after_map(semtsdf_vol* v, hipStream_t s) {
     if (!v->map_set || v->map_stream == s) return SEMTSDF_OK;
     v->multi_stream = true;
-    if (!v->bmin_ev_set) {
-        if (!v->bmin_ev) HIPC(hipEventCreateWithFlags(&v->bmin_ev, order_event_flags()));
-        HIPC(hipEventRecord(v->bmin_ev, v->map_stream));  // everything queued there so far
-        v->bmin_ev_set = true;
+    if (!v->maps_ev_set) {
+        if (!v->maps_ev) HIPC(hipEventCreateWithFlags(&v->maps_ev, order_event_flags()));
+        HIPC(hipEventRecord(v->maps_ev, v->map_stream));  // everything queued there so far
+        v->maps_ev_set = true;
     }
-    HIPC(hipStreamWaitEvent(s, v->bmin_ev, 0));
+    HIPC(hipStreamWaitEvent(s, v->maps_ev, 0));
     return SEMTSDF_OK;
 }
 
@@ -544,28 +544,28 @@ int order_after_map(semtsdf_vol* v, hipStream_t s) {
 // update runs on the stream of the first march that needs it; marches on other streams (a
 // render overlapping the next frame's association) and the next writer of the volume are
 // ordered after it (order_after_map).
-int ensure_bmin(semtsdf_vol* v, hipStream_t s) {
+int ensure_maps(semtsdf_vol* v, hipStream_t s) {
     if (int rc = order_after_map(v, s)) return rc;
-    if (!v->bmin_dirty && !v->bmin_stale) return SEMTSDF_OK;
+    if (!v->maps_dirty && !v->maps_stale) return SEMTSDF_OK;
     // stale (reset/upload): every brick; dirty (integrate): the bricks the cull marked
-    HIPC(launch_brick_min(v->g, v->b, v->bmin_stale, s));
+    HIPC(launch_brick_min(v->g, v->b, v->maps_stale, s));
     v->map_stream = s;
     v->map_set = true;
-    v->bmin_ev_set = false;
+    v->maps_ev_set = false;
     // on a stream other than the volume's own, record now: that stream may be gone (a
     // caller's temporary render stream) by the time another stream needs the ordering
     if (v->multi_stream || s != v->stream) {
-        if (!v->bmin_ev) HIPC(hipEventCreateWithFlags(&v->bmin_ev, order_event_flags()));
-        HIPC(hipEventRecord(v->bmin_ev, s));
-        v->bmin_ev_set = true;
+        if (!v->maps_ev) HIPC(hipEventCreateWithFlags(&v->maps_ev, order_event_flags()));
+        HIPC(hipEventRecord(v->maps_ev, s));
+        v->maps_ev_set = true;
     }
-    v->bmin_dirty = false;
-    v->bmin_stale = false;
+    v->maps_dirty = false;
+    v->maps_stale = false;
     return SEMTSDF_OK;
 }
 
 // A writer of the volume (integrate, upload, reset) orders itself after the last map update.
-int after_bmin(semtsdf_vol* v, hipStream_t s) { return order_after_map(v, s); }
+int after_maps(semtsdf_vol* v, hipStream_t s) { return order_after_map(v, s); }
 
 // The association tables in their cleared state before a frame's statistics: one init
 // launch unless the last decide left them cleared.
@@ -605,7 +605,7 @@ int associate_impl(semtsdf_vol* v, uint8_t* mask_d, const float E[16], hipStream
     if (v->n_obs == 0) return fail(SEMTSDF_ERR_STATE, "association needs n_obs > 0 (tsdf.cu:426)");
     EventPair ep;
     timing_begin(v, v->ev_assoc, s, &ep);
-    if (int rc = ensure_bmin(v, s)) return rc;
+    if (int rc = ensure_maps(v, s)) return rc;
     if (int rc = tables_ready(v, s)) return rc;
     HIPC(launch_mask_stats(mask_d, (int)npx(v), v->tables_d, s));
     AssocArgs a{};
@@ -623,7 +623,7 @@ int associate_impl(semtsdf_vol* v, uint8_t* mask_d, const float E[16], hipStream
     int order_n = 0;  // the decision orders the fused march's next launch (largest tiles first)
     if (view) {
         RenderArgs r = *view;
-        r.b = v->b;  // the map buffers as ensure_bmin left them
+        r.b = v->b;  // the map buffers as ensure_maps left them
         const int n = ((a.width + 15) / 16) * ((a.height + 15) / 16) + ((r.width + 15) / 16) * ((r.height + 15) / 16);
         if (n <= 8192 && n > v->tile_cap) {  // tile_order sorts up to 8192 tiles (256 x kTileOrderPer)
             for (unsigned** q : {&v->tile_cost_d, &v->tile_perm_d})
@@ -938,7 +938,6 @@ int semtsdf_create(const semtsdf_params* p, int device, semtsdf_vol** out) {
     g.ty = g.nuz * 256u;
     g.tx = g.nuy * g.ty;
     g.nbx = (g.dimx + 7) / 8; g.nby = (g.dimy + 7) / 8; g.nbz = (g.lz + 7) / 8;
-    g.nsx = (g.nbx + 7) / 8; g.nsy = (g.nby + 7) / 8; g.nsz = (g.nbz + 7) / 8;
     for (int i = 0; i < 3; ++i) g.rvox[i] = 1.0f / g.voxel[i];  // IEEE: correctly rounded
     const size_t n = g.nvox;
     const size_t px = (size_t)p->width * p->height;
@@ -954,10 +953,7 @@ int semtsdf_create(const semtsdf_params* p, int device, semtsdf_vol** out) {
     if ((rc = dev_alloc(v, (void**)&v->b.wt, n * 4))) return bail(rc);
     if ((rc = dev_alloc(v, (void**)&v->b.sflag, n / 32 + 1))) return bail(rc);
     const size_t nbricks = (size_t)g.nbx * g.nby * g.nbz;
-    if ((rc = dev_alloc(v, (void**)&v->b.bmin, nbricks * 4))) return bail(rc);
     if ((rc = dev_alloc(v, (void**)&v->b.bplain, nbricks * 4))) return bail(rc);
-    if ((rc = dev_alloc(v, (void**)&v->b.sbmin, (size_t)g.nsx * g.nsy * g.nsz * 4))) return bail(rc);
-    if ((rc = dev_alloc(v, (void**)&v->b.bdist, nbricks))) return bail(rc);
     if ((rc = dev_alloc(v, (void**)&v->b.boct, nbricks * 8))) return bail(rc);
     if ((rc = dev_alloc(v, (void**)&v->b.botmp, nbricks * 8))) return bail(rc);
     const size_t nquads = (size_t)g.nbx * g.nby * (size_t)((g.nbz + 3) / 4);
@@ -1082,7 +1078,7 @@ int semtsdf_reset(semtsdf_vol* v, void* stream) {
     HIPC(hipSetDevice(v->device));
     hipStream_t s = pick(v, stream);
     const size_t n = v->g.nvox;
-    if (int rc = after_bmin(v, s)) return rc;
+    if (int rc = after_maps(v, s)) return rc;
     HIPC(launch_fill_volume(v->g, v->b, v->p.flags, s));
     HIPC(hipMemsetAsync(v->b.wt, 0, n * 4, s));
     HIPC(hipMemsetAsync(v->b.sflag, 0, n / 32 + 1, s));  // steady flags: unknown
@@ -1096,7 +1092,7 @@ int semtsdf_reset(semtsdf_vol* v, void* stream) {
     v->votes_dropped_seen = 0;
     v->n_obs = 0;
     v->wmax_bound = 0;
-    v->bmin_stale = true;
+    v->maps_stale = true;
     return SEMTSDF_OK;
 }
 
@@ -1276,7 +1272,7 @@ int semtsdf_assoc_probs(semtsdf_vol* v, const float E[16], float* probs, uint8_t
     a.tables = v->tables_d;
     a.probs_out = v->probs_d;
     a.box_out = v->box_d;
-    if (int rc = ensure_bmin(v, s)) return rc;
+    if (int rc = ensure_maps(v, s)) return rc;
     HIPC(launch_assoc_march(a, s));
     HIPC(hipMemcpyAsync(probs, v->probs_d, n * 4, hipMemcpyDeviceToHost, s));
     HIPC(hipMemcpyAsync(box_mask, v->box_d, n, hipMemcpyDeviceToHost, s));
@@ -1395,7 +1391,7 @@ static int parse_frame_dev_impl(semtsdf_vol* v, const uint16_t* depth_d, const u
     // the next frame's association (and a live view) march this state: refresh the
     // empty-space map now, on this stream, so a view on another stream ordered after this
     // call and the next association on this stream both find it current
-    if (sem) return ensure_bmin(v, s);
+    if (sem) return ensure_maps(v, s);
     return SEMTSDF_OK;
 }
 
@@ -1466,7 +1462,7 @@ int semtsdf_shard_ray_begin(semtsdf_vol* v, int kind, const float cam[16], const
         m.use_s2w = 1;
         v->ray_cam = m;
     }
-    if (int rc = ensure_bmin(v, v->stream)) return rc;
+    if (int rc = ensure_maps(v, v->stream)) return rc;
     HIPC(hipStreamSynchronize(v->stream));  // the protocol's steps may run on another stream
     v->ray_kind = kind;
     v->assoc_ray_done = false;
@@ -1725,7 +1721,7 @@ static int raycast_impl(semtsdf_vol* v, const float s2w[16], const float c[3], i
     RenderArgs a;
     if (int rc = render_args(v, s2w, c, mode, out_bgr_d, out_t_d, a)) return rc;
     EventPair ep;
-    if (int rc = ensure_bmin(v, s)) return rc;
+    if (int rc = ensure_maps(v, s)) return rc;
     a.b = v->b;
     // instrumentation: SEMTSDF_RAY_STATS=<file> appends per-pixel march counters and
     // per-wave timestamps of every render
@@ -1753,7 +1749,7 @@ static int raycast_impl(semtsdf_vol* v, const float s2w[16], const float c[3], i
 }
 
 static int launch_view(semtsdf_vol* v, const RenderArgs& view, hipStream_t s) {
-    if (int rc = ensure_bmin(v, s)) return rc;
+    if (int rc = ensure_maps(v, s)) return rc;
     RenderArgs a = view;
     a.b = v->b;
     HIPC(launch_render(a, s));
@@ -1906,10 +1902,10 @@ int semtsdf_upload(semtsdf_vol* v, const float* sdf, const int32_t* wt, const vo
     HIPC(hipSetDevice(v->device));
     hipStream_t s = v->stream;
     int rc;
-    if ((rc = after_bmin(v, s))) return rc;
+    if ((rc = after_maps(v, s))) return rc;
     // derived maps first: a transfer that fails half-way must not leave steady flags or an
     // empty-space map that describe the old contents (0 = unknown is always safe)
-    v->bmin_stale = true;
+    v->maps_stale = true;
     if (sdf || wt) HIPC(hipMemsetAsync(v->b.sflag, 0, v->g.nvox / 32 + 1, s));  // steady flags: unknown
     if (sdf && (rc = vox_xfer(v, const_cast<float*>(sdf), v->b.sdf, false, "sdf", s, 0, nref(v)))) return rc;
     if (wt && (rc = vox_xfer(v, const_cast<int32_t*>(wt), v->b.wt, false, "weight", s, 0, nref(v)))) return rc;
@@ -1960,7 +1956,7 @@ int semtsdf_upload(semtsdf_vol* v, const float* sdf, const int32_t* wt, const vo
         HIPC(hipFree(stage));
         HIPC(launch_hist_mask(v->g, v->b, s));
     }
-    v->bmin_stale = true;
+    v->maps_stale = true;
     HIPC(hipStreamSynchronize(s));
     return SEMTSDF_OK;
 }
@@ -1969,10 +1965,8 @@ int semtsdf_map_words(semtsdf_vol* v, uint64_t* out, uint64_t capacity, uint64_t
     if (!v || !count) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
     HIPC(hipSetDevice(v->device));
     hipStream_t s = v->stream;
-    const bool dist = v->b.bdist && v->b.boct && v->b.botmp;
-    *count = dist ? (uint64_t)v->g.nbx * v->g.nby * v->g.nbz : 0u;
-    if (!dist) return SEMTSDF_OK;
-    if (int rc = ensure_bmin(v, s)) return rc;  // the maps of the current state
+    *count = (uint64_t)v->g.nbx * v->g.nby * v->g.nbz;
+    if (int rc = ensure_maps(v, s)) return rc;  // the maps of the current state
     const uint64_t n = std::min<uint64_t>(capacity, *count);
     if (out && n) HIPC(hipMemcpyAsync(out, v->b.boct, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
@@ -1986,7 +1980,7 @@ int semtsdf_export_surface(semtsdf_vol* v, float sdf_max, int32_t min_weight, se
     if (!(sdf_max > 0.0f)) return fail(SEMTSDF_ERR_INVALID, "sdf_max must be > 0");
     HIPC(hipSetDevice(v->device));
     hipStream_t s = v->stream;
-    if (int rc = after_bmin(v, s)) return rc;
+    if (int rc = after_maps(v, s)) return rc;
     unsigned long long* cnt_d = nullptr;
     HIPC(hipMalloc((void**)&cnt_d, sizeof(unsigned long long)));
     SurfacePoint* pts_d = nullptr;
@@ -2033,7 +2027,7 @@ int semtsdf_extract_mesh(semtsdf_vol* v, int32_t min_weight, semtsdf_mesh_vertex
     if (!verts != !tris) return fail(SEMTSDF_ERR_INVALID, "verts and tris must both be given or both be NULL");
     HIPC(hipSetDevice(v->device));
     hipStream_t s = v->stream;
-    if (int rc = after_bmin(v, s)) return rc;
+    if (int rc = after_maps(v, s)) return rc;
     const uint64_t nb = mesh_blocks(v->g);
     // scratch of the call, one allocation per pass: 29 B per 256-voxel tile to count; 4 B per stored
     // voxel and the outputs to emit
@@ -2107,7 +2101,7 @@ int semtsdf_instance_stats(semtsdf_vol* v, float sdf_max, int32_t min_weight, se
     if (!(v->p.flags & SEMTSDF_F_SEMANTIC)) return fail(SEMTSDF_ERR_UNSUPPORTED, "instance stats need a SEMANTIC volume");
     HIPC(hipSetDevice(v->device));
     hipStream_t s = v->stream;
-    if (int rc = after_bmin(v, s)) return rc;
+    if (int rc = after_maps(v, s)) return rc;
     constexpr size_t rec_bytes = kMaxObjects * sizeof(InstanceRec), ov_bytes = kMaxObjects * kMaxObjects * sizeof(uint64_t);
     char* scratch = nullptr;  // the records, then the overlap table
     hipError_t e = hipMalloc((void**)&scratch, rec_bytes + ov_bytes);
@@ -2146,7 +2140,7 @@ int semtsdf_remap_instances(semtsdf_vol* v, const uint8_t* lut, int32_t num_objs
     // the volume's writer, ordered as the integrate is: after the last empty-space map update;
     // the frame work queued before it on s (a lagged view and the association march read the
     // histogram in the launches of parse_frame_view_dev) precedes it in stream order
-    if (int rc = after_bmin(v, s)) return rc;
+    if (int rc = after_maps(v, s)) return rc;
     // the current next id lives on the device (the decisions advance it there)
     int cur = 0;
     HIPC(hipMemcpyAsync(&cur, v->num_objs_d, sizeof(int), hipMemcpyDeviceToHost, s));

@@ -38,7 +38,6 @@ struct VolGeom {
     uint32_t nuy, nuz;         // 8-row y groups and 32-plane z groups (one 256-voxel tile each)
     uint32_t tx, ty;           // tile-index strides of x (nuy * nuz * 256) and of y / 8 (nuz * 256)
     int nbx, nby, nbz;         // 8^3 bricks of the local storage (empty-space map)
-    int nsx, nsy, nsz;         // 64^3 super-bricks (8^3 bricks each)
     float rvox[3];             // RN(1 / voxel) per axis (exact divisions by the voxel size)
 };
 
@@ -69,15 +68,14 @@ struct VolBufs {
                        // interpolate only the bins set at one of their 8 corners)
     int32_t* cls;      // vote mode
     int32_t* cls_cnt;  // vote mode
-    float* bmin;       // per 8^3 brick: min sdf over its voxels and the +1 border (ray skipping)
-    float* bplain;     // per 8^3 brick: min sdf over its own voxels
-    float* sbmin;      // per 64^3 super-brick (8^3 bricks): min of bmin over its bricks
-    uint8_t* bdist;    // per 8^3 brick: L-inf distance in bricks to the nearest non-skippable
-                       // brick (0: not skippable), capped at kBrickDistCap
-    uint64_t* boct;    // per 8^3 brick, byte o: the same distance within octant o only (bit a of o
-                       // set: negative along axis a), so a ray heading into octant o may step
-                       // through the box reaching that many bricks ahead of it (bdist = the min)
-    uint64_t* botmp;   // scratch of the distance passes
+    float* bplain;     // per 8^3 brick: min sdf over its own voxels (kept for the incremental map update);
+                       // a brick is skippable when the min over it and its +1 neighbours (every voxel
+                       // a sample based in it reads) reaches the marches' skip threshold
+    uint64_t* boct;    // the empty-space map, per 8^3 brick, byte o: L-inf distance in bricks to the
+                       // nearest non-skippable brick within octant o (bit a of o set: negative along
+                       // axis a; 0: not skippable; capped at kBrickDistCap), so a ray heading into
+                       // octant o may step through the box reaching that many bricks ahead of it
+    uint64_t* botmp;   // scratch of the distance passes (the skippable seed, then the x and y passes)
     uint32_t* bdirty;  // per quad of 4 z-consecutive 8^3 bricks ((bx, by, bz/4), z fastest): bit j set when
                        // a voxel of brick 4q + j crossed the skip threshold since the last map update
     uint32_t* dlist;   // [1 + quads]: count, then the quads whose dirty word is nonzero

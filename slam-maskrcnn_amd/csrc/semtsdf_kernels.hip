@@ -28,6 +28,7 @@
 #include <stdlib.h>
 #include "semtsdf_internal.h"
 #include "semtsdf_libm.h"
+#include "semtsdf_steps.h"
 
 namespace semtsdf {
 
@@ -200,9 +201,9 @@ hipError_t launch_min_i64(long long* dst, const long long* src, size_t n, hipStr
 // its 64 (x, y) rows, two float4 loads) writes the min of sdf over the brick's own voxels;
 // with all == 0 only bricks the integrate marked dirty are recomputed (a voxel of theirs
 // crossed the skip threshold, the only change that can flip the map; the stale minima of
-// the other bricks stay on their side of it).  k_brick_dilate: bmin[b] = min of the
-// plain map over b + {0,1}^3, which covers [8b, 8b + 8] per axis: every voxel a trilinear
-// sample based in brick b reads.
+// the other bricks stay on their side of it).  k_brick_dilate: brick b is skippable when
+// the min of the plain map over b + {0,1}^3 reaches the skip threshold; that covers
+// [8b, 8b + 8] per axis: every voxel a trilinear sample based in brick b reads.
 // One wave per 4 z-consecutive bricks (a quad): lane = one (x, y) row of 32 voxels = one
 // whole 128-B line (a row of a single brick is only 32 B of a line).  `want` bit j: recompute
 // brick 4q + j.
@@ -268,7 +269,8 @@ __global__ __launch_bounds__(256) void k_brick_plain(VolGeom g, const float* __r
 
 __device__ __forceinline__ float skip_threshold(const VolGeom& g);
 
-__global__ __launch_bounds__(256) void k_brick_dilate(VolGeom g, const float* __restrict__ plain, float* __restrict__ bmin,
+// d0: the seed of the distance passes (0 = not skippable, cap = skippable, in every byte)
+__global__ __launch_bounds__(256) void k_brick_dilate(VolGeom g, const float* __restrict__ plain,
                                                       uint64_t* __restrict__ d0, uint32_t* __restrict__ dlist) {
     const unsigned nb = (unsigned)g.nbx * g.nby * g.nbz;
     const unsigned br = blockIdx.x * blockDim.x + threadIdx.x;
@@ -282,8 +284,7 @@ __global__ __launch_bounds__(256) void k_brick_dilate(VolGeom g, const float* __
                 const int xx = bx + i, yy = by + j, zz = bz + k;
                 if (xx < g.nbx && yy < g.nby && zz < g.nbz) m = fminf(m, plain[((unsigned)xx * g.nby + yy) * g.nbz + zz]);
             }
-    bmin[br] = m;
-    if (d0) d0[br] = m >= skip_threshold(g) ? (uint64_t)kBrickDistCap * 0x0101010101010101ull : 0ull;
+    d0[br] = m >= skip_threshold(g) ? (uint64_t)kBrickDistCap * 0x0101010101010101ull : 0ull;
 }
 
 // Octant brick distance maps, one axis per pass: for octant o (bit a set: negative along axis
@@ -291,8 +292,7 @@ __global__ __launch_bounds__(256) void k_brick_dilate(VolGeom g, const float* __
 // axis (neighbours inside the volume).  Three passes (x, y, z) from d0 (0 = not skippable, cap
 // = skippable, in every byte) give, per octant, the L-inf distance to the nearest non-skippable
 // brick of that octant, capped: the box of the d bricks from b on along each of the octant's
-// directions is skippable.  The last pass also writes the symmetric distance (the min over
-// the octants: every brick lies in some octant of b) for the sharded march.
+// directions is skippable.
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));  // v_pk_*_u16 operands
 
 // Octant bytes of a map word in four packed registers of two u16 lanes: R[0] = octants (0, 2),
@@ -321,7 +321,7 @@ __device__ __forceinline__ void oct_unpack(uint64_t wp, uint64_t wn, u16x2 R[4])
 // (v_pk_max_u16 / v_pk_min_u16: 2 octants per operation).
 template <int AXIS>
 __global__ __launch_bounds__(256) void k_brick_oct_axis(VolGeom g, const uint64_t* __restrict__ in,
-                                                        uint64_t* __restrict__ out, uint8_t* __restrict__ sym) {
+                                                        uint64_t* __restrict__ out) {
     const unsigned nb = (unsigned)g.nbx * g.nby * g.nbz;
     const unsigned br = blockIdx.x * blockDim.x + threadIdx.x;
     if (br >= nb) return;
@@ -362,28 +362,6 @@ __global__ __launch_bounds__(256) void k_brick_oct_axis(VolGeom g, const uint64_
     const uint32_t lo = (uint32_t)d[0].x | ((uint32_t)d[1].x << 8) | ((uint32_t)d[0].y << 16) | ((uint32_t)d[1].y << 24);
     const uint32_t hi = (uint32_t)d[2].x | ((uint32_t)d[3].x << 8) | ((uint32_t)d[2].y << 16) | ((uint32_t)d[3].y << 24);
     out[br] = (uint64_t)lo | ((uint64_t)hi << 32);
-    if (sym) {
-        const u16x2 m = __builtin_elementwise_min(__builtin_elementwise_min(d[0], d[1]),
-                                                  __builtin_elementwise_min(d[2], d[3]));
-        sym[br] = (uint8_t)min(min((int)m.x, (int)m.y), kBrickDistCap);
-    }
-}
-
-// Super-brick level: sbmin[s] = min of bmin over the (up to) 8^3 bricks of super-brick s,
-// so it bounds every trilinear sample based in its 64^3 voxels.  One wave per super-brick.
-__global__ __launch_bounds__(256) void k_brick_super(VolGeom g, const float* __restrict__ bmin, float* __restrict__ sbmin) {
-    const unsigned ns = (unsigned)g.nsx * g.nsy * g.nsz;
-    const unsigned sb = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (sb >= ns) return;
-    const int lane = threadIdx.x & 63;
-    const int sz = sb % g.nsz, sy = (sb / g.nsz) % g.nsy, sx = sb / (g.nsz * g.nsy);
-    float m = 3.0e38f;
-    const int bx = sx * 8 + (lane >> 3), by = sy * 8 + (lane & 7);  // lane = one (x, y) brick column
-    if (bx < g.nbx && by < g.nby)
-        for (int k = 0; k < 8 && sz * 8 + k < g.nbz; ++k)
-            m = fminf(m, bmin[((unsigned)bx * g.nby + (unsigned)by) * g.nbz + (unsigned)(sz * 8 + k)]);
-    for (int off = 32; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
-    if (lane == 0) sbmin[sb] = m;
 }
 
 hipError_t launch_brick_min(const VolGeom& g, const VolBufs& b, bool all, hipStream_t s) {
@@ -393,17 +371,11 @@ hipError_t launch_brick_min(const VolGeom& g, const VolBufs& b, bool all, hipStr
     const unsigned nw = all ? nq : (nq < 4096u ? nq : 4096u);  // waves (list mode: grid-strided)
     hipLaunchKernelGGL(k_brick_plain, dim3((nw + 3) / 4), dim3(256), 0, s, g, b.sdf, b.bplain, b.bdirty, b.dlist,
                        all ? 1 : 0);
-    const bool dist = b.bdist && b.boct && b.botmp;
-    hipLaunchKernelGGL(k_brick_dilate, dim3((nb + 255) / 256), dim3(256), 0, s, g, b.bplain, b.bmin,
-                       dist ? b.botmp : nullptr, b.dlist);
-    if (dist) {  // d0 in botmp -> x -> boct -> y -> botmp -> z -> boct (+ bdist)
-        hipLaunchKernelGGL(k_brick_oct_axis<0>, dim3((nb + 255) / 256), dim3(256), 0, s, g, b.botmp, b.boct, nullptr);
-        hipLaunchKernelGGL(k_brick_oct_axis<1>, dim3((nb + 255) / 256), dim3(256), 0, s, g, b.boct, b.botmp, nullptr);
-        hipLaunchKernelGGL(k_brick_oct_axis<2>, dim3((nb + 255) / 256), dim3(256), 0, s, g, b.botmp, b.boct, b.bdist);
-    } else {
-        const unsigned ns = (unsigned)g.nsx * g.nsy * g.nsz;
-        if (b.sbmin && ns) hipLaunchKernelGGL(k_brick_super, dim3((ns + 3) / 4), dim3(256), 0, s, g, b.bmin, b.sbmin);
-    }
+    // d0 in botmp -> x -> boct -> y -> botmp -> z -> boct
+    hipLaunchKernelGGL(k_brick_dilate, dim3((nb + 255) / 256), dim3(256), 0, s, g, b.bplain, b.botmp, b.dlist);
+    hipLaunchKernelGGL(k_brick_oct_axis<0>, dim3((nb + 255) / 256), dim3(256), 0, s, g, b.botmp, b.boct);
+    hipLaunchKernelGGL(k_brick_oct_axis<1>, dim3((nb + 255) / 256), dim3(256), 0, s, g, b.boct, b.botmp);
+    hipLaunchKernelGGL(k_brick_oct_axis<2>, dim3((nb + 255) / 256), dim3(256), 0, s, g, b.botmp, b.boct);
     return hipGetLastError();
 }
 
@@ -2168,15 +2140,17 @@ __device__ __forceinline__ bool ray_bounds(const VolGeom& g, float ox, float oy,
 // evaluated; t still advances by the same additions, so the result is unchanged.
 __device__ __forceinline__ float skip_threshold(const VolGeom& g) { return g.voxel[0] / 2.0f * (1.0f + 0x1p-16f); }
 
-// Sample evaluator with the brick map: returns false (and no value) when the sample's
-// brick is known to hold only values >= thr.  Caches the last brick looked up.
+// The last brick a march looked up in the octant distance map, and its skip box.
 struct SkipCursor {
-    int brick = -1;      // brick of the last lookup, or -2 - s while super-brick s is skipped
-    bool skip = false;
-    int sb = -1;         // super-brick of the last lookup
-    bool sskip = false;
-    float lo[3], hi[3];  // approximate voxel-coordinate box surely inside the skippable (super-)brick
+    int brick = -1;      // brick of the last lookup
+    bool skip = false;   // that brick holds only values >= the skip threshold
+    float lo[3], hi[3];  // approximate voxel-coordinate box surely inside the skippable bricks around it
 };
+
+// Octant of a ray direction (bit a set: negative along axis a): the byte of a map word to read.
+__device__ __forceinline__ int ray_octant(float dx, float dy, float dz) {
+    return (dx < 0.0f ? 1 : 0) | (dy < 0.0f ? 2 : 0) | (dz < 0.0f ? 4 : 0);
+}
 
 // Approximate voxel coordinates of a ray point (|error| ~1e-4 voxel; only used to prove
 // that a sample lies well inside a brick already known to be skippable).
@@ -2199,7 +2173,7 @@ __device__ __forceinline__ RayVox ray_vox(const VolGeom& g, float ox, float oy, 
 // Ray parameter where the ray leaves the cursor's box (computed with the same approximate
 // voxel coordinates; samples before it are inside the box, which is itself a margin inside
 // the skippable brick).
-__device__ __forceinline__ float skip_box_exit(const SkipCursor& cur, const RayVox& rv) {
+__device__ __forceinline__ float box_exit(const SkipCursor& cur, const RayVox& rv) {
     float te = 3.0e38f;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -2211,131 +2185,56 @@ __device__ __forceinline__ float skip_box_exit(const SkipCursor& cur, const RayV
     return te * (1.0f - 0x1p-16f);
 }
 
-// t += step repeated while t < tend, as the march's single additions would do it, in O(1)
-// per binade of t: inside a binade [2^e, 2^(e+1)) every t is a multiple of its ulp, so
-// RN(t + step) = t + d with the same d = RN_ulp(step) for every t there (unless step is an
-// exact tie between two multiples of the ulp, which takes single steps), and t + n d is
-// exact while it stays below 2^(e+1).  The addition that crosses into the next binade is
-// done singly.  On return t >= tend (or t is unchanged when it already was) and t_prev is
-// the value before the last addition.
-__device__ __forceinline__ void skip_steps(float& t, float& t_prev, float step, float tend) {
-    while (t < tend) {
-        const float t1 = t + step;
-        if (!(t1 < tend)) {  // one more sample ends the run
-            t_prev = t;
-            t = t1;
-            break;
-        }
-        const int eb = __float_as_int(t) & 0x7F800000;
-        const float ulp = __int_as_float(eb - (23 << 23)), top = __int_as_float(eb + (1 << 23));
-        const float d = t1 - t;  // exact (t1 within a factor 2 of t)
-        const float lim = fminf(tend, top);
-        int n = 0;
-        if (fabsf(step - d) * 2.0f != ulp && t1 < top) {
-            n = (int)((lim - t) * __builtin_amdgcn_rcpf(d));  // estimate, fixed up exactly below
-            n = max(n, 1);
-            while (n > 1 && !(t + (float)n * d < lim)) --n;
-            while (t + (float)(n + 1) * d < lim) ++n;
-        }
-        if (n <= 1) {  // a tie, or the next addition leaves the binade: single step
-            t_prev = t;
-            t = t1;
-            continue;
-        }
-        t_prev = t + (float)(n - 1) * d;
-        t = t + (float)n * d;
-    }
-}
-
-__device__ __forceinline__ bool in_skip_box(const SkipCursor& cur, const RayVox& rv, float t) {
+__device__ __forceinline__ bool in_box(const SkipCursor& cur, const RayVox& rv, float t) {
     const float ax = fmaf(t, rv.k[0], rv.c[0]), ay = fmaf(t, rv.k[1], rv.c[1]), az = fmaf(t, rv.k[2], rv.c[2]);
     return (ax > cur.lo[0]) & (ax < cur.hi[0]) & (ay > cur.lo[1]) & (ay < cur.hi[1]) & (az > cur.lo[2]) &
            (az < cur.hi[2]);
 }
 
-// Evaluates the sample at p unless the brick map proves it >= voxel/2 (returns false).
-// Caches the last brick looked up and, with `box`, the conservative voxel-coordinate box
-// of a skippable brick for in_skip_box.
-__device__ __forceinline__ void skip_box(const VolGeom& g, SkipCursor& cur, int x0, int y0, int z0, int n, bool lx,
-                                         bool hx, bool ly, bool hy, bool lz, bool hz) {
-    // (super-)brick bounds in voxel coordinates, shrunk by a margin far above the
-    // approximation error of RayVox; the outer faces of the volume extend to infinity
-    // (samples there clamp into the edge brick)
+// The cursor's box for a skippable brick (bx, by) whose first plane is global plane zb, at
+// distance r > 0 (bricks) from the nearest non-skippable brick of octant oct: the r^3 bricks
+// from it on towards the ray's direction are skippable, one box for the march to step
+// through.  Bounds in global voxel coordinates, shrunk by a margin far above the approximation
+// error of RayVox; the outer faces of the volume extend to infinity (samples there clamp into
+// the edge brick).  [zlo, zhi): planes to clip the box to; an empty clip leaves no box
+// (in_box is false everywhere).
+__device__ __forceinline__ void brick_box(const VolGeom& g, SkipCursor& cur, int bx, int by, int zb, int oct, int r,
+                                          int zlo = INT_MIN, int zhi = INT_MAX) {
+    const int x0 = bx - ((oct & 1) ? r - 1 : 0), x1 = bx + ((oct & 1) ? 1 : r);  // bricks, x1 exclusive
+    const int y0 = by - ((oct & 2) ? r - 1 : 0), y1 = by + ((oct & 2) ? 1 : r);
+    const int z0 = max(zb - ((oct & 4) ? r - 1 : 0) * 8, zlo), z1 = min(zb + ((oct & 4) ? 1 : r) * 8, zhi);  // planes
     const float m = 0.01f;
-    cur.lo[0] = lx ? -1e30f : (float)x0 + m;
-    cur.hi[0] = hx ? 1e30f : (float)(x0 + n) - m;
-    cur.lo[1] = ly ? -1e30f : (float)y0 + m;
-    cur.hi[1] = hy ? 1e30f : (float)(y0 + n) - m;
-    cur.lo[2] = lz ? -1e30f : (float)z0 + m;
-    cur.hi[2] = hz ? 1e30f : (float)(z0 + n) - m;
+    if (z0 < z1) {
+        cur.lo[0] = x0 <= 0 ? -1e30f : (float)(x0 * 8) + m;
+        cur.hi[0] = x1 >= g.nbx ? 1e30f : (float)(x1 * 8) - m;
+        cur.lo[1] = y0 <= 0 ? -1e30f : (float)(y0 * 8) + m;
+        cur.hi[1] = y1 >= g.nby ? 1e30f : (float)(y1 * 8) - m;
+        cur.lo[2] = z0 <= 0 ? -1e30f : (float)z0 + m;
+        cur.hi[2] = z1 >= g.dimz ? 1e30f : (float)z1 - m;
+    } else {
+        cur.lo[0] = 1e30f;
+        cur.hi[0] = -1e30f;
+    }
 }
 
-// OCT: the volume has its octant distance maps (a single volume's marches, known on the
-// host), so the other map modes are not compiled in.
-template <bool SH = true, bool OCT = false>
-__device__ __forceinline__ bool sample_or_skip(const VolGeom& g, const VolBufs& b, float thr, SkipCursor& cur,
-                                               float px, float py, float pz, float* f, bool box = false,
-                                               int oct = -1) {
-    const TriCoord c = tri_coord<SH>(g, px, py, pz);
-    if (OCT || (box && b.bdist)) {
-        // the brick's distance r to the nearest non-skippable brick of the ray's octant: the
-        // r^3 bricks from it on towards the ray's direction are skippable, one box for the
-        // march to step through (without an octant: the (2r-1)^3 bricks around it)
-        const int br = brick_of(g, c);
-        if (br != cur.brick) {
-            cur.brick = br;
-            const int r = (OCT || oct >= 0) ? (int)reinterpret_cast<const uint8_t*>(b.boct)[(size_t)br * 8 + oct]
-                                            : b.bdist[br];
-            cur.skip = r > 0;
-            if (cur.skip) {
-                const int bx = c.xc >> 3, by = c.yc >> 3, bz = c.zl >> 3;
-                const int nx = oct < 0 || (oct & 1), ny = oct < 0 || (oct & 2), nz = oct < 0 || (oct & 4);
-                const int px_ = oct < 0 || !(oct & 1), py_ = oct < 0 || !(oct & 2), pz_ = oct < 0 || !(oct & 4);
-                const int x0 = bx - (nx ? r - 1 : 0), y0 = by - (ny ? r - 1 : 0), z0 = bz - (nz ? r - 1 : 0);
-                const int x1 = bx + (px_ ? r : 1), y1 = by + (py_ ? r : 1), z1 = bz + (pz_ ? r : 1);  // exclusive
-                const float m = 0.01f;
-                cur.lo[0] = x0 <= 0 ? -1e30f : (float)(x0 * 8) + m;
-                cur.hi[0] = x1 >= g.nbx ? 1e30f : (float)(x1 * 8) - m;
-                cur.lo[1] = y0 <= 0 ? -1e30f : (float)(y0 * 8) + m;
-                cur.hi[1] = y1 >= g.nby ? 1e30f : (float)(y1 * 8) - m;
-                cur.lo[2] = z0 <= 0 ? -1e30f : (float)(z0 * 8) + m;
-                cur.hi[2] = z1 >= g.nbz ? 1e30f : (float)(z1 * 8) - m;
-            }
-        }
-        if (cur.skip) return false;
-        *f = tri_eval(b.sdf, tri_from(g, c));
-        return true;
+// Distance byte of brick br in the map of octant oct (0: the brick is not skippable).
+__device__ __forceinline__ int brick_dist(const VolBufs& b, int br, int oct) {
+    return (int)reinterpret_cast<const uint8_t*>(b.boct)[(size_t)br * 8 + oct];
+}
+
+// Single volume: evaluates the sample at p unless the octant map proves it >= voxel/2
+// (returns false, and no value).  Caches the last brick looked up and its skip box.
+__device__ __forceinline__ bool sample_or_skip(const VolGeom& g, const VolBufs& b, SkipCursor& cur, float px, float py,
+                                               float pz, float* f, int oct) {
+    const TriCoord c = tri_coord<false>(g, px, py, pz);
+    const int br = brick_of(g, c);
+    if (br != cur.brick) {
+        cur.brick = br;
+        const int r = brick_dist(b, br, oct);
+        cur.skip = r > 0;
+        if (cur.skip) brick_box(g, cur, c.xc >> 3, c.yc >> 3, c.zl & ~7, oct, r);
     }
-    if (b.bmin) {
-        if (box && b.sbmin) {  // super-brick level first: one lookup per 64^3 voxels of free space
-            const int sx = c.xc >> 6, sy = c.yc >> 6, sz = c.zl >> 6;
-            const int sb = (int)__umul24(__umul24((unsigned)sx, (unsigned)g.nsy) + (unsigned)sy, (unsigned)g.nsz) + sz;
-            if (sb != cur.sb) {
-                cur.sb = sb;
-                cur.sskip = b.sbmin[sb] >= thr;
-            }
-            if (cur.sskip) {
-                if (cur.brick != -2 - sb) {
-                    cur.brick = -2 - sb;
-                    cur.skip = true;
-                    skip_box(g, cur, sx * 64, sy * 64, sz * 64, 64, sx == 0, sx == g.nsx - 1, sy == 0, sy == g.nsy - 1,
-                             sz == 0, sz == g.nsz - 1);
-                }
-                return false;
-            }
-        }
-        const int br = brick_of(g, c);
-        if (br != cur.brick) {
-            cur.brick = br;
-            cur.skip = b.bmin[br] >= thr;
-            if (cur.skip && box) {
-                const int bx = c.xc >> 3, by = c.yc >> 3, bz = c.zl >> 3;
-                skip_box(g, cur, bx * 8, by * 8, bz * 8, 8, bx == 0, bx == g.nbx - 1, by == 0, by == g.nby - 1,
-                         bz == 0, bz == g.nbz - 1);
-            }
-        }
-        if (cur.skip) return false;
-    }
+    if (cur.skip) return false;
     *f = tri_eval(b.sdf, tri_from(g, c));
     return true;
 }
@@ -2351,23 +2250,21 @@ struct MarchStats {
 #endif
 constexpr int kMarchSpec = SEMTSDF_MARCH_SPEC;  // speculative samples per evaluated sample
 
-template <bool OCT>
+// Single volumes only (the host rejects sharded handles).
 __device__ bool march_ray(const VolGeom& g, const VolBufs& b, float ox, float oy, float oz, float dx, float dy,
                           float dz, float* t_hit, MarchStats* st = nullptr) {
     float t, tfar;
     if (!ray_bounds(g, ox, oy, oz, dx, dy, dz, &t, &tfar)) return false;
     const float vx = g.voxel[0];
-    const float thr = skip_threshold(g);
     SkipCursor cur;
     const RayVox rv = ray_vox(g, ox, oy, oz, dx, dy, dz);
-    const bool box = OCT || b.bmin != nullptr;  // single-volume marches only (the host rejects sharded handles)
-    const int oct = OCT || b.boct ? (dx < 0.0f ? 1 : 0) | (dy < 0.0f ? 2 : 0) | (dz < 0.0f ? 4 : 0) : -1;
+    const int oct = ray_octant(dx, dy, dz);
     float f_t = 1.0f, f_tt = 0.0f;
     bool prev_skipped = false;  // f_t not evaluated: re-evaluate it at t_prev if needed
     float t_prev = t;
     {
         float f;
-        if (sample_or_skip<false, OCT>(g, b, thr, cur, fmaf(t, dx, ox), fmaf(t, dy, oy), fmaf(t, dz, oz), &f, box, oct)) {
+        if (sample_or_skip(g, b, cur, fmaf(t, dx, ox), fmaf(t, dy, oy), fmaf(t, dz, oz), &f, oct)) {
             if (!(f > 0.0f)) return false;
             f_t = f;
         } else {
@@ -2380,12 +2277,12 @@ __device__ bool march_ray(const VolGeom& g, const VolBufs& b, float ox, float oy
     // lanes of a wave do not wait for each other's memory round trips sample by sample.
     while (t < tfar) {
         if (st) st->iters++;
-        if (box && cur.skip && in_skip_box(cur, rv, t)) {
+        if (cur.skip && in_box(cur, rv, t)) {
             // the same additions as sample-by-sample stepping (the hit position depends on
             // them), tested against the box's exit parameter, then exactly near the exit
-            const float tend = fminf(tfar, skip_box_exit(cur, rv));
-            skip_steps(t, t_prev, step, tend);
-            while (t < tfar && in_skip_box(cur, rv, t)) {
+            const float tend = fminf(tfar, box_exit(cur, rv));
+            skip_steps<false>(t, t_prev, step, tend);
+            while (t < tfar && in_box(cur, rv, t)) {
                 t_prev = t;
                 t += step;
                 if (st) st->skipped++;
@@ -2397,7 +2294,7 @@ __device__ bool march_ray(const VolGeom& g, const VolBufs& b, float ox, float oy
         float f;
         const int brick_before = cur.brick;
         const bool evaluated =
-            sample_or_skip<false, OCT>(g, b, thr, cur, fmaf(t, dx, ox), fmaf(t, dy, oy), fmaf(t, dz, oz), &f, box, oct);
+            sample_or_skip(g, b, cur, fmaf(t, dx, ox), fmaf(t, dy, oy), fmaf(t, dz, oz), &f, oct);
         if (st) {
             st->lookups += cur.brick != brick_before;
             st->evals += evaluated;
@@ -2676,13 +2573,7 @@ __device__ __forceinline__ void assoc_pixel_out(const AssocPixels& px, int npx, 
 #define SEMTSDF_MARCH_WPE 1  // no occupancy request (register-limited: 3 waves per SIMD)
 #endif
 
-// The single-volume marches take the octant-map specialisation when the volume has the maps.
-inline bool oct_maps(const VolBufs& b) {
-    return b.bmin && b.bdist && b.boct;
-}
-
 // One 16x16-pixel tile (bx, by) of the association march, a whole workgroup.
-template <bool OCT>
 __device__ __forceinline__ void assoc_tile(const AssocArgs& a, AssocLds& s, int bx, int by) {
     const int tid = threadIdx.x;
     assoc_lds_clear(s);
@@ -2701,7 +2592,7 @@ __device__ __forceinline__ void assoc_tile(const AssocArgs& a, AssocLds& s, int 
 #pragma unroll
         for (int k = 0; k < kMaxObjects; ++k) p[k] = 0.0f;
         unsigned bins = 0;
-        if (march_ray<OCT>(a.g, a.b, ox, oy, oz, dx, dy, dz, &t)) {
+        if (march_ray(a.g, a.b, ox, oy, oz, dx, dy, dz, &t)) {
             const Tri tr = tri_setup<false>(a.g, fmaf(t, dx, ox), fmaf(t, dy, oy), fmaf(t, dz, oz));
             bins = tri_hist(a.g, a.b, tr, p);
         }
@@ -2737,18 +2628,14 @@ __device__ __forceinline__ void assoc_tile(const AssocArgs& a, AssocLds& s, int 
     if (tid == 0 && s.pos) atomicMax(&T->pos_max, s.pos);
 }
 
-template <bool OCT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEMTSDF_MARCH_WPE))) void k_assoc_march(AssocArgs a) {
     __shared__ AssocLds s;
-    assoc_tile<OCT>(a, s, (int)blockIdx.x, (int)blockIdx.y);
+    assoc_tile(a, s, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 hipError_t launch_assoc_march(const AssocArgs& a, hipStream_t s) {
     const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-    if (oct_maps(a.b))
-        hipLaunchKernelGGL(k_assoc_march<true>, grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL(k_assoc_march<false>, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_assoc_march, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -3464,7 +3351,7 @@ __device__ __forceinline__ void shade_hit(const VolGeom& g, const VolBufs& vb, c
 // STATS: instrumentation build of the kernel (a run-time select of the stats pointer would
 // keep MarchStats in scratch memory)
 // One 16x16-pixel tile (bx, by) of a render, a whole workgroup.
-template <bool STATS, bool OCT>
+template <bool STATS>
 __device__ __forceinline__ void render_tile(const RenderArgs& a, int bx, int by) {
     const int x = bx * 16 + (threadIdx.x & 15);
     const int y = by * 16 + (threadIdx.x >> 4);
@@ -3477,7 +3364,7 @@ __device__ __forceinline__ void render_tile(const RenderArgs& a, int bx, int by)
     float th = -1.0f;
     MarchStats ms;
     const uint64_t t_start = STATS ? __builtin_amdgcn_s_memrealtime() : 0;
-    if (march_ray<OCT>(a.g, a.b, ox, oy, oz, dx, dy, dz, &t, STATS ? &ms : nullptr)) {
+    if (march_ray(a.g, a.b, ox, oy, oz, dx, dy, dz, &t, STATS ? &ms : nullptr)) {
         th = t;
         const Tri tr = tri_setup<false>(a.g, fmaf(t, dx, ox), fmaf(t, dy, oy), fmaf(t, dz, oz));
         shade_hit(a.g, a.b, tr, a.mode, a.color_i32, a.palette, &b, &gch, &r);
@@ -3500,9 +3387,9 @@ __device__ __forceinline__ void render_tile(const RenderArgs& a, int bx, int by)
     }
 }
 
-template <bool STATS, bool OCT>
+template <bool STATS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEMTSDF_MARCH_WPE))) void k_render(RenderArgs a) {
-    render_tile<STATS, OCT>(a, (int)blockIdx.x, (int)blockIdx.y);
+    render_tile<STATS>(a, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // A render of the volume and the association march of the next frame in one launch: both
@@ -3510,7 +3397,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEMTSDF_MAR
 // view of frame k shows), and both are bound by their slowest rays, so one grid lets the
 // tiles of each fill the other's tail.  Workgroup b: tiles alternate (association, render)
 // while both have tiles left, then the rest of the larger one.
-template <bool OCT>
 #ifndef SEMTSDF_FUSED_WPE
 #define SEMTSDF_FUSED_WPE 4  // 4 waves per SIMD: at most 128 VGPRs (the association's per-pixel output put it at 131)
 #endif
@@ -3532,10 +3418,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEMTSDF_FUS
     }
     if (assoc) {
         const int tx = (aa.width + 15) / 16;
-        assoc_tile<OCT>(aa, s, t % tx, t / tx);
+        assoc_tile(aa, s, t % tx, t / tx);
     } else {
         const int tx = (ra.width + 15) / 16;
-        render_tile<false, OCT>(ra, t % tx, t / tx);
+        render_tile<false>(ra, t % tx, t / tx);
     }
     if (aa.tile_cost) {  // the tile's duration (100 MHz ticks), all its waves done
         __syncthreads();
@@ -3546,22 +3432,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEMTSDF_FUS
 hipError_t launch_march_fused(const AssocArgs& aa, const RenderArgs& ra, hipStream_t s) {
     const int na = ((aa.width + 15) / 16) * ((aa.height + 15) / 16);
     const int nr = ((ra.width + 15) / 16) * ((ra.height + 15) / 16);
-    if (oct_maps(aa.b))
-        hipLaunchKernelGGL(k_march_fused<true>, dim3(na + nr), dim3(256), 0, s, aa, ra, na, nr);
-    else
-        hipLaunchKernelGGL(k_march_fused<false>, dim3(na + nr), dim3(256), 0, s, aa, ra, na, nr);
+    hipLaunchKernelGGL(k_march_fused, dim3(na + nr), dim3(256), 0, s, aa, ra, na, nr);
     return hipGetLastError();
 }
 
 hipError_t launch_render(const RenderArgs& a, hipStream_t s) {
     const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
     if (a.ray_stats)
-        hipLaunchKernelGGL((k_render<true, false>), grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_render<true>, grid, dim3(256), 0, s, a);
     else
-        if (oct_maps(a.b))
-            hipLaunchKernelGGL((k_render<false, true>), grid, dim3(256), 0, s, a);
-        else
-            hipLaunchKernelGGL((k_render<false, false>), grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_render<false>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -3601,64 +3481,6 @@ __device__ __forceinline__ int2 gather_min(const int2* __restrict__ g, int n, in
     return best;
 }
 
-// t += step repeated n times (t > 0), in O(1) per binade of t: the closed form of skip_steps
-// (inside a binade every RN(t + step) adds the same d, so m additions are t + m d while the
-// result stays in the binade; ties and binade crossings are single additions).
-__device__ __forceinline__ float advance_n(float t, float step, int n) {
-    while (n > 0) {
-        const float t1 = t + step;
-        const int eb = __float_as_int(t) & 0x7F800000;
-        const float ulp = __int_as_float(eb - (23 << 23)), top = __int_as_float(eb + (1 << 23));
-        const float d = t1 - t;  // exact (t1 within a factor 2 of t)
-        int m = 0;
-        if (fabsf(step - d) * 2.0f != ulp && t1 < top) {
-            m = min(max((int)((top - t) * __builtin_amdgcn_rcpf(d)), 1), n);  // estimate, fixed up below
-            while (m > 1 && !(t + (float)m * d < top)) --m;
-        }
-        if (m <= 1) {
-            t = t1;
-            --n;
-            continue;
-        }
-        t = t + (float)m * d;
-        n -= m;
-    }
-    return t;
-}
-
-// skip_steps counting its additions in n (t stops at the first value >= tend)
-__device__ __forceinline__ void skip_steps_n(float& t, float step, float tend, int& n) {
-    while (t < tend) {
-        const float t1 = t + step;
-        if (!(t1 < tend)) {
-            t = t1;
-            ++n;
-            break;
-        }
-        const int eb = __float_as_int(t) & 0x7F800000;
-        const float ulp = __int_as_float(eb - (23 << 23)), top = __int_as_float(eb + (1 << 23));
-        const float d = t1 - t;
-        const float lim = fminf(tend, top);
-        int m = 0;
-        if (fabsf(step - d) * 2.0f != ulp && t1 < top) {
-            m = max((int)((lim - t) * __builtin_amdgcn_rcpf(d)), 1);
-            while (m > 1 && !(t + (float)m * d < lim)) --m;
-            while (t + (float)(m + 1) * d < lim) ++m;
-        }
-        if (m <= 1) {
-            t = t1;
-            ++n;
-            continue;
-        }
-        t = t + (float)m * d;
-        n += m;
-    }
-}
-
-__device__ __forceinline__ float replay_t(float t, int ncoarse, int nfine, float vx) {
-    return advance_n(advance_n(t, vx, ncoarse), vx / 4.0f, nfine);
-}
-
 struct RayGeo {
     float ox, oy, oz, dx, dy, dz, t0, t1;
     bool in;
@@ -3681,59 +3503,30 @@ __device__ __forceinline__ float sample_at(const ShardRayArgs& a, const RayGeo& 
 }
 
 // false when the brick map proves the sample >= voxel/2 (see march_ray).  A skippable brick
-// also leaves a box in the cursor, in global voxel coordinates: its distance box ((2r-1)^3
-// bricks of the local distance map, or the brick alone without one) clipped in z to the
-// sample's chunk block and, inside it, to the base planes w < chunk (their +1 plane is stored:
-// the halo at most; local bricks across a block boundary are not global neighbours).  Every
-// sample inside the box is >= voxel/2 whoever owns it, so the march steps through it with
-// exact additions.
-__device__ __forceinline__ bool sample_at_skip(const ShardRayArgs& a, const RayGeo& r, float t, float thr,
-                                               SkipCursor& cur, float* f) {
+// also leaves a box in the cursor, in global voxel coordinates: its distance box in the local
+// map of the ray's octant, clipped in z to the sample's chunk block and, inside it, to the
+// base planes w < chunk (their +1 plane is stored: the halo at most; local bricks across a
+// block boundary are not global neighbours).  Every sample inside the box is >= voxel/2
+// whoever owns it, so the march steps through it with exact additions.
+__device__ __forceinline__ bool sample_at_skip(const ShardRayArgs& a, const RayGeo& r, float t, SkipCursor& cur,
+                                               float* f) {
     const VolGeom& g = a.g;
     const TriCoord c = tri_coord(g, fmaf(t, r.dx, r.ox), fmaf(t, r.dy, r.oy), fmaf(t, r.dz, r.oz));
-    if (a.b.bmin) {
-        const int br = brick_of(g, c);
-        if (br != cur.brick) {
-            cur.brick = br;
-            int rad = 0;
-            const int oct = a.b.boct ? (r.dx < 0.0f ? 1 : 0) | (r.dy < 0.0f ? 2 : 0) | (r.dz < 0.0f ? 4 : 0) : -1;
-            if (a.b.bdist) {
-                rad = oct >= 0 ? (int)reinterpret_cast<const uint8_t*>(a.b.boct)[(size_t)br * 8 + oct] : a.b.bdist[br];
-                cur.skip = rad > 0;
-            } else {
-                cur.skip = a.b.bmin[br] >= thr;
-                rad = cur.skip ? 1 : 0;
-            }
-            cur.lo[0] = 1e30f;  // no box unless set below
-            cur.hi[0] = -1e30f;
-            if (cur.skip) {
-                const int bx = c.xc >> 3, by = c.yc >> 3, bz = c.zl >> 3;
-                const int per = g.nshards > 1 ? g.chunk + g.halo : g.lz;  // local planes per chunk block
-                const int blk0 = g.nshards > 1 ? c.zl / per * per : 0;   // first local plane of the block
-                const int own = g.nshards > 1 ? g.chunk : g.lz;          // base planes w < own in the block
-                // the box: rad bricks along each axis on the ray's side (both sides without an
-                // octant map or with the brick alone)
-                const bool sym = oct < 0;
-                const int nx = sym || (oct & 1) ? rad - 1 : 0, px_ = sym || !(oct & 1) ? rad : 1;
-                const int ny = sym || (oct & 2) ? rad - 1 : 0, py_ = sym || !(oct & 2) ? rad : 1;
-                const int nz = sym || (oct & 4) ? rad - 1 : 0, pz_ = sym || !(oct & 4) ? rad : 1;
-                const int lz0 = max((bz - nz) * 8, blk0), lz1 = min((bz + pz_) * 8, blk0 + own);  // local, excl.
-                if (lz0 < lz1) {
-                    const int gz0 = local_to_global_z(g, blk0) + (lz0 - blk0);
-                    const int gz1 = gz0 + (lz1 - lz0);
-                    const int x0 = bx - nx, y0 = by - ny, x1 = bx + px_, y1 = by + py_;
-                    const float m = 0.01f;
-                    cur.lo[0] = x0 <= 0 ? -1e30f : (float)(x0 * 8) + m;
-                    cur.hi[0] = x1 >= g.nbx ? 1e30f : (float)(x1 * 8) - m;
-                    cur.lo[1] = y0 <= 0 ? -1e30f : (float)(y0 * 8) + m;
-                    cur.hi[1] = y1 >= g.nby ? 1e30f : (float)(y1 * 8) - m;
-                    cur.lo[2] = gz0 <= 0 ? -1e30f : (float)gz0 + m;
-                    cur.hi[2] = gz1 >= g.dimz ? 1e30f : (float)gz1 - m;
-                }
-            }
+    const int br = brick_of(g, c);
+    if (br != cur.brick) {
+        cur.brick = br;
+        const int oct = ray_octant(r.dx, r.dy, r.dz);
+        const int rad = brick_dist(a.b, br, oct);
+        cur.skip = rad > 0;
+        if (cur.skip) {
+            const int per = g.nshards > 1 ? g.chunk + g.halo : g.lz;  // local planes per chunk block
+            const int blk0 = g.nshards > 1 ? c.zl / per * per : 0;   // first local plane of the block
+            const int own = g.nshards > 1 ? g.chunk : g.lz;          // base planes w < own in the block
+            const int gblk0 = local_to_global_z(g, blk0);            // the block's first plane, global
+            brick_box(g, cur, c.xc >> 3, c.yc >> 3, gblk0 + ((c.zl & ~7) - blk0), oct, rad, gblk0, gblk0 + own);
         }
-        if (cur.skip) return false;
     }
+    if (cur.skip) return false;
     *f = tri_eval(a.b.sdf, tri_from(g, c));
     return true;
 }
@@ -3766,6 +3559,43 @@ __device__ __forceinline__ bool next_owned_t(const ShardRayArgs& a, const RayGeo
     return true;
 }
 
+// One phase of the sharded march: from sample n at t on, in steps of `step`, the record of this
+// shard's first owned sample with f < event, or the "ran out" record (key INT_MAX).  The samples
+// of the owned chunks only: skip boxes and runs of foreign samples are jumped with exact
+// additions (sample n is still the start plus `step` added n times).
+__device__ __forceinline__ int2 shard_march(const ShardRayArgs& a, const RayGeo& r, SkipCursor cur, float t, float step,
+                                            float event, int n) {
+    const RayVox rv = ray_vox(a.g, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
+    float tp;  // unused: the sample before a hit is fetched by a later step
+    while (t < r.t1) {
+        if (cur.skip && in_box(cur, rv, t)) {  // skippable bricks: no event inside
+            n += skip_steps<false>(t, tp, step, fminf(r.t1, box_exit(cur, rv)));
+            while (t < r.t1 && in_box(cur, rv, t)) {
+                t += step;
+                ++n;
+            }
+            continue;
+        }
+        if (owns_at(a, r, t)) {
+            float f;
+            if (sample_at_skip(a, r, t, cur, &f) && f < event) return mk_rec(n, __float_as_int(f));
+            t += step;
+            ++n;
+            continue;
+        }
+        float tend;
+        if (!next_owned_t(a, r, t, &tend)) break;
+        tend = fminf(tend, r.t1);
+        if (t < tend) {
+            n += skip_steps<false>(t, tp, step, tend);
+        } else {
+            t += step;
+            ++n;
+        }
+    }
+    return mk_rec(INT_MAX, 0);
+}
+
 __global__ __launch_bounds__(256) void k_shard_ray_step(ShardRayArgs a) {
     const int x = blockIdx.x * 16 + (threadIdx.x & 15);
     const int y = blockIdx.y * 16 + (threadIdx.x >> 4);
@@ -3779,53 +3609,11 @@ __global__ __launch_bounds__(256) void k_shard_ray_step(ShardRayArgs a) {
         if (!r.in) {
             rec = mk_rec(-1, 0);
         } else {
-            float t = r.t0;
-            bool dead = false;
-            const float thr = skip_threshold(a.g);
             SkipCursor cur;
-            const RayVox rv = ray_vox(a.g, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
             float f0;
-            if (owns_at(a, r, t) && sample_at_skip(a, r, t, thr, cur, &f0)) {
-                if (!(f0 > 0.0f)) { rec = mk_rec(-1, 0); dead = true; }
-            }
-            if (!dead) {
-                if (!(t < r.t1)) {
-                    rec = mk_rec(-1, 0);
-                } else {
-                    // the samples of the owned chunks only: runs of foreign samples are jumped
-                    // with exact additions (sample k is still t0 + vx added k times)
-                    int k = 0;
-                    while (t < r.t1) {
-                        if (cur.skip && in_skip_box(cur, rv, t)) {  // a skippable brick: no event inside
-                            skip_steps_n(t, vx, fminf(r.t1, skip_box_exit(cur, rv)), k);
-                            while (t < r.t1 && in_skip_box(cur, rv, t)) {
-                                t += vx;
-                                ++k;
-                            }
-                            continue;
-                        }
-                        if (owns_at(a, r, t)) {
-                            float f;
-                            if (sample_at_skip(a, r, t, thr, cur, &f) && f < vx / 2.0f) {
-                                rec = mk_rec(k, __float_as_int(f));
-                                break;
-                            }
-                            t += vx;
-                            ++k;
-                            continue;
-                        }
-                        float tend;
-                        if (!next_owned_t(a, r, t, &tend)) break;
-                        tend = fminf(tend, r.t1);
-                        if (t < tend) {
-                            skip_steps_n(t, vx, tend, k);
-                        } else {
-                            t += vx;
-                            ++k;
-                        }
-                    }
-                }
-            }
+            // the first sample's owner rejects the ray when it is not in front of the surface
+            const bool dead = owns_at(a, r, r.t0) && sample_at_skip(a, r, r.t0, cur, &f0) && !(f0 > 0.0f);
+            rec = dead || !(r.t0 < r.t1) ? mk_rec(-1, 0) : shard_march(a, r, cur, r.t0, vx, vx / 2.0f, 0);
         }
     } else if (a.step == 1) {
         const int2 c = gather_min(a.gathered, a.nrec, npx, px);
@@ -3841,42 +3629,9 @@ __global__ __launch_bounds__(256) void k_shard_ray_step(ShardRayArgs a) {
                 const float t = replay_t(r.t0, k - 1, 0, vx);
                 if (owns_at(a, r, t)) rec = mk_rec(0, __float_as_int(sample_at(a, r, t)));
             } else {
-                float t = replay_t(r.t0, k, 0, vx);
+                // sample j of the quarter-step march is t_k + q added j times, from j = 1 on
                 const float q = vx / 4.0f;
-                const float thr = skip_threshold(a.g);
-                SkipCursor cur;
-                const RayVox rv = ray_vox(a.g, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
-                int j = 1;  // sample j of the quarter-step march is t_k + q added j times
-                t += q;
-                while (t < r.t1) {
-                    if (cur.skip && in_skip_box(cur, rv, t)) {
-                        skip_steps_n(t, q, fminf(r.t1, skip_box_exit(cur, rv)), j);
-                        while (t < r.t1 && in_skip_box(cur, rv, t)) {
-                            t += q;
-                            ++j;
-                        }
-                        continue;
-                    }
-                    if (owns_at(a, r, t)) {
-                        float f;
-                        if (sample_at_skip(a, r, t, thr, cur, &f) && f < 0.0f) {
-                            rec = mk_rec(j, __float_as_int(f));
-                            break;
-                        }
-                        t += q;
-                        ++j;
-                        continue;
-                    }
-                    float tend;
-                    if (!next_owned_t(a, r, t, &tend)) break;
-                    tend = fminf(tend, r.t1);
-                    if (t < tend) {
-                        skip_steps_n(t, q, tend, j);
-                    } else {
-                        t += q;
-                        ++j;
-                    }
-                }
+                rec = shard_march(a, r, SkipCursor(), replay_t(r.t0, k, 0, vx) + q, q, 0.0f, 1);
             }
         }
     } else {  // step 2
