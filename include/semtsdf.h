@@ -321,6 +321,39 @@ int semtsdf_shard_note_integrated(semtsdf_vol* v, const uint8_t* mask_d, void* s
 int semtsdf_masks_to_labels(const uint8_t* masks_d, int width, int height, int n, int min_area,
                             uint8_t* labels_d, int* n_kept, void* stream);
 
+/* The same labels straight from the detector's pixel boxes and mini-masks, without the [height][width][n]
+ * masks: detection i's mask is unmold_mask's (mrcnn/utils.py:565-581: skimage.transform.resize order=1
+ * mode="constant" of the mini-mask to the box, without anti-aliasing as in the reference's era, then
+ * >= 0.5), evaluated per pixel by the rule below; keep, rank and label are exactly those of
+ * semtsdf_masks_to_labels (area > min_area; the smallest kept detection that is on at the pixel; equal
+ * areas: the lower index; label 1 + index among the kept, wrapping as u8).
+ *   boxes_d: [n][4] int32 pixel boxes (y1, x1, y2, x2), half-open, as unmold_detections / denorm_boxes
+ *            leave them.  y2 <= y1 or x2 <= x1: an empty detection (area 0).  A box may reach outside the
+ *            image; only the pixels inside both the box and the image exist.
+ *   mini_d:  [n][mh][mw], each detection's own mask (its class already selected); dtype 0 fp16, 1 bf16,
+ *            2 f32, every element converted to f32 exactly; 1 <= mh, mw <= 64
+ *   0 <= n <= 256; width, height as semtsdf_masks_to_labels
+ *   labels_d: u8 [height * width], every pixel written (n == 0: all zero)
+ *   areas_d: u32 [n] or NULL: the number of `on` pixels of each detection
+ *   work_d:  semtsdf_detections_to_labels_workspace(n) bytes of device memory
+ *   n_kept:  optional, host: the number of kept detections (synchronises)
+ * The rule, every operation rounded to f32 on its own (no fused multiply-add), for detection i with
+ * h = y2 - y1, w = x2 - x1 and image pixel (y, x), max(y1, 0) <= y < min(y2, height) (likewise x):
+ *   sy = (float)mh / (float)h;                   sx = (float)mw / (float)w
+ *   cy = ((float)(y - y1) + 0.5f) * sy - 0.5f;   cx likewise
+ *   y0 = floorf(cy), fy = cy - y0, taps iy = (int)y0 and iy + 1 (x likewise); a tap outside
+ *   [0, mh) x [0, mw) reads 0.0f
+ *   top = m[iy][ix] * (1.0f - fx) + m[iy][ix+1] * fx;  bot = m[iy+1][ix] * (1.0f - fx) + m[iy+1][ix+1] * fx
+ *   v = top * (1.0f - fy) + bot * fy;  on = v >= 0.5f (a NaN is off)
+ * The call allocates nothing and enqueues kernels only on stream (it can be recorded in a captured HIP
+ * graph); it is asynchronous unless n_kept is given.  Argument errors return
+ * SEMTSDF_ERR_INVALID before any device work.  Deterministic: integer sums, one writer per pixel. */
+size_t semtsdf_detections_to_labels_workspace(int n);
+int semtsdf_detections_to_labels(const int32_t* boxes_d, const void* mini_d, int dtype, int mh, int mw,
+                                 int n, int width, int height, int min_area, uint8_t* labels_d,
+                                 uint32_t* areas_d /* [n] or NULL */, void* work_d,
+                                 int* n_kept /* host, optional: synchronises */, void* stream);
+
 /* Achievable HBM bandwidth on `device` (GB/s, read + write bytes) of a float4 device copy
  * of `bytes` bytes, best of `reps` runs: the practical ceiling beside the 8 TB/s spec peak. */
 int semtsdf_copy_bandwidth(int device, size_t bytes, int reps, double* gbs);

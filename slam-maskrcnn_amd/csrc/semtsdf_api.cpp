@@ -1637,6 +1637,33 @@ int semtsdf_masks_to_labels(const uint8_t* masks_d, int width, int height, int n
     return SEMTSDF_OK;
 }
 
+size_t semtsdf_detections_to_labels_workspace(int n) {
+    (void)n;  // the per-detection tables are sized for kMaxDetections
+    return mask_scratch_bytes();
+}
+
+int semtsdf_detections_to_labels(const int32_t* boxes_d, const void* mini_d, int dtype, int mh, int mw, int n,
+                                 int width, int height, int min_area, uint8_t* labels_d, uint32_t* areas_d,
+                                 void* work_d, int* n_kept, void* stream) {
+    if (!labels_d) return fail(SEMTSDF_ERR_INVALID, "labels is NULL");
+    if (!work_d) return fail(SEMTSDF_ERR_INVALID, "workspace is NULL");
+    if (n < 0 || n > kMaxDetections) return fail(SEMTSDF_ERR_INVALID, "n=%d detections outside [0, %d]", n, kMaxDetections);
+    if ((!boxes_d || !mini_d) && n > 0) return fail(SEMTSDF_ERR_INVALID, "boxes or mini-masks NULL");
+    if (dtype < 0 || dtype > 2) return fail(SEMTSDF_ERR_INVALID, "dtype=%d is not 0 (fp16), 1 (bf16) or 2 (f32)", dtype);
+    if (mh < 1 || mh > 64 || mw < 1 || mw > 64) return fail(SEMTSDF_ERR_INVALID, "mini-mask %dx%d outside [1, 64]", mh, mw);
+    if (width <= 0 || height <= 0 || (int64_t)width * height > (1 << 28)) return fail(SEMTSDF_ERR_INVALID, "bad size");
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(launch_detections_to_labels(boxes_d, mini_d, dtype, mh, mw, n, width, height, min_area, work_d, labels_d,
+                                     areas_d, s));
+    if (n_kept) {
+        unsigned k = 0;
+        HIPC(hipMemcpyAsync(&k, (char*)work_d + mask_scratch_kept_offset(), sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        *n_kept = (int)k;
+    }
+    return SEMTSDF_OK;
+}
+
 int semtsdf_min_i64(int64_t* dst_d, const int64_t* src_d, size_t n, void* stream) {
     if (!dst_d || !src_d) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
     HIPC(launch_min_i64((long long*)dst_d, (const long long*)src_d, n, (hipStream_t)stream));

@@ -322,6 +322,11 @@ hipError_t launch_masks_to_labels(const uint8_t* masks, int npx, int n, int min_
                                   hipStream_t s);
 size_t mask_scratch_bytes();
 size_t mask_scratch_kept_offset();
+// pixel boxes [n][4] + mini-masks [n][mh][mw] (dtype 0 fp16, 1 bf16, 2 f32) -> u8 labels by the paste rule
+// of include/semtsdf.h and the same dmask.py rule; scratch of mask_scratch_bytes(); areas [n] or null
+hipError_t launch_detections_to_labels(const int32_t* boxes, const void* mini, int dtype, int mh, int mw, int n,
+                                       int width, int height, int min_area, void* scratch, uint8_t* out,
+                                       uint32_t* areas, hipStream_t s);
 hipError_t launch_brick_min(const VolGeom& g, const VolBufs& b, bool all, hipStream_t s);
 hipError_t launch_fill_volume(const VolGeom& g, const VolBufs& b, uint32_t flags, hipStream_t s);
 hipError_t launch_depth_pyramid(const uint16_t* depth, const uint8_t* rgb, uint8_t* mask, int w, int h,

@@ -4109,6 +4109,167 @@ hipError_t launch_masks_to_labels(const uint8_t* masks, int npx, int n, int min_
 size_t mask_scratch_bytes() { return sizeof(MaskScratch); }
 size_t mask_scratch_kept_offset() { return offsetof(MaskScratch, n_kept); }
 
+// ------------------------------------------------------------------------------------
+// Detections -> labels without the [H][W][N] masks (semtsdf_detections_to_labels): each
+// detection's mini-mask is resized to its pixel box as unmold_mask does (mrcnn/utils.py:565-581,
+// skimage resize order=1 mode="constant" without anti-aliasing, >= 0.5) by the paste rule of
+// include/semtsdf.h, evaluated where it is needed: once per box pixel for the areas, and per
+// image pixel over the kept boxes in rank order for the labels.  Both passes decide a pixel in
+// paste_on(), so an area is the count of the pixels the label pass can paint; the decision between
+// them is k_mask_decide's.
+// ------------------------------------------------------------------------------------
+struct PasteBox {
+    int y1, x1, y2, x2;
+};
+
+// element k of a mini-mask array of fp16 (0), bf16 (1) or f32 (2) values, widened exactly
+struct MiniGlobal {
+    const void* base;
+    int dtype;
+    __device__ __forceinline__ float operator()(size_t k) const {
+        if (dtype == 0) return (float)((const _Float16*)base)[k];
+        if (dtype == 1) return __uint_as_float((unsigned)((const unsigned short*)base)[k] << 16);
+        return ((const float*)base)[k];
+    }
+};
+
+struct MiniLds {
+    const float* base;
+    __device__ __forceinline__ float operator()(size_t k) const { return base[k]; }
+};
+
+__device__ __forceinline__ float paste_scale(int mini, long long extent) { return (float)mini / (float)extent; }
+
+// The paste rule for image pixel (y, x) inside box b (extents positive): every operation rounded to f32
+// on its own (the file is built with -ffp-contract=off); a tap outside the mini-mask reads 0.0f and
+// still takes part in the arithmetic.
+template <class Mini>
+__device__ __forceinline__ bool paste_on(const Mini& m, int mh, int mw, const PasteBox& b, float sy, float sx, int y,
+                                         int x) {
+    const float cy = ((float)((long long)y - b.y1) + 0.5f) * sy - 0.5f;
+    const float cx = ((float)((long long)x - b.x1) + 0.5f) * sx - 0.5f;
+    const float y0 = floorf(cy), x0 = floorf(cx);
+    const float fy = cy - y0, fx = cx - x0;
+    const int iy = (int)y0, ix = (int)x0;
+    const bool ya = iy >= 0 && iy < mh, yb = iy + 1 >= 0 && iy + 1 < mh;
+    const bool xa = ix >= 0 && ix < mw, xb = ix + 1 >= 0 && ix + 1 < mw;
+    const size_t r0 = (size_t)(ya ? iy : 0) * mw, r1 = (size_t)(yb ? iy + 1 : 0) * mw;
+    const size_t c0 = (size_t)(xa ? ix : 0), c1 = (size_t)(xb ? ix + 1 : 0);
+    const float m00 = ya && xa ? m(r0 + c0) : 0.0f;
+    const float m01 = ya && xb ? m(r0 + c1) : 0.0f;
+    const float m10 = yb && xa ? m(r1 + c0) : 0.0f;
+    const float m11 = yb && xb ? m(r1 + c1) : 0.0f;
+    const float top = m00 * (1.0f - fx) + m01 * fx;
+    const float bot = m10 * (1.0f - fx) + m11 * fx;
+    const float v = top * (1.0f - fy) + bot * fy;
+    return v >= 0.5f;  // a NaN is off
+}
+
+__global__ __launch_bounds__(256) void k_paste_clear(MaskScratch* __restrict__ sc) {
+    sc->area[threadIdx.x] = 0u;  // rank, label and n_kept are written by k_mask_decide
+}
+
+constexpr int kPasteMaxMini = 64;    // mini-mask side accepted (an f32 copy is 16 KB of LDS)
+constexpr int kPasteAreaBlocks = 32; // workgroups striding over one detection's clipped box
+
+// One workgroup per (detection blockIdx.y, 256-pixel run of its clipped box, strided by gridDim.x);
+// an empty or fully clipped box, and the runs past a small one, leave before touching the mini-mask.
+__global__ __launch_bounds__(256) void k_paste_areas(const PasteBox* __restrict__ boxes, const void* __restrict__ mini,
+                                                     int dtype, int mh, int mw, int width, int height,
+                                                     MaskScratch* __restrict__ sc) {
+    __shared__ float s_mini[kPasteMaxMini * kPasteMaxMini];
+    __shared__ unsigned s_count;
+    const int i = blockIdx.y;
+    const PasteBox b = boxes[i];
+    if (b.y2 <= b.y1 || b.x2 <= b.x1) return;
+    const int cy0 = b.y1 > 0 ? b.y1 : 0, cx0 = b.x1 > 0 ? b.x1 : 0;
+    const int cy1 = b.y2 < height ? b.y2 : height, cx1 = b.x2 < width ? b.x2 : width;
+    if (cy1 <= cy0 || cx1 <= cx0) return;
+    const int cw = cx1 - cx0;
+    const int total = (cy1 - cy0) * cw;  // <= width * height <= 2^28
+    if ((int)blockIdx.x * 256 >= total) return;
+    const int msz = mh * mw;
+    const MiniGlobal g{mini, dtype};
+    for (int k = threadIdx.x; k < msz; k += 256) s_mini[k] = g((size_t)i * msz + k);
+    if (threadIdx.x == 0) s_count = 0u;
+    __syncthreads();
+    const MiniLds m{s_mini};
+    const float sy = paste_scale(mh, (long long)b.y2 - b.y1), sx = paste_scale(mw, (long long)b.x2 - b.x1);
+    unsigned count = 0;  // wave-uniform
+    for (int base = blockIdx.x * 256; base < total; base += gridDim.x * 256) {
+        const int p = base + (int)threadIdx.x;
+        bool on = false;
+        if (p < total) {
+            const int ry = p / cw;
+            on = paste_on(m, mh, mw, b, sy, sx, cy0 + ry, cx0 + (p - ry * cw));
+        }
+        count += (unsigned)__popcll(__ballot(on));
+    }
+    if ((threadIdx.x & 63) == 0 && count) atomicAdd(&s_count, count);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_count) atomicAdd(&sc->area[i], s_count);
+}
+
+// One lane per pixel, consecutive lanes on consecutive x.  The kept detections' boxes, scales, indices
+// and labels sit in LDS in rank order (smallest area first); a pixel takes the first one that is on.
+__global__ __launch_bounds__(256) void k_paste_labels(const PasteBox* __restrict__ boxes, const void* __restrict__ mini,
+                                                      int dtype, int mh, int mw, int n, int width, int height,
+                                                      const MaskScratch* __restrict__ sc, uint8_t* __restrict__ out,
+                                                      unsigned* __restrict__ areas) {
+    __shared__ PasteBox s_box[kMaxDetections];
+    __shared__ float s_sy[kMaxDetections], s_sx[kMaxDetections];
+    __shared__ unsigned short s_idx[kMaxDetections];
+    __shared__ unsigned char s_label[kMaxDetections];
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const unsigned r = sc->rank[i];
+        if (r != 0xFFFFu) {  // kept: its area is positive, so its box has positive extents
+            const PasteBox b = boxes[i];
+            s_box[r] = b;
+            s_sy[r] = paste_scale(mh, (long long)b.y2 - b.y1);
+            s_sx[r] = paste_scale(mw, (long long)b.x2 - b.x1);
+            s_idx[r] = (unsigned short)i;
+            s_label[r] = sc->label[i];
+        }
+        if (areas && blockIdx.x == 0) areas[i] = sc->area[i];
+    }
+    __syncthreads();
+    const int kept = (int)sc->n_kept;
+    const int p = blockIdx.x * 256 + (int)threadIdx.x;
+    if (p >= width * height) return;
+    const int y = p / width, x = p - y * width;
+    const int msz = mh * mw;
+    unsigned char lab = 0;
+    for (int r = 0; r < kept; ++r) {
+        const PasteBox b = s_box[r];
+        if (y < b.y1 || y >= b.y2 || x < b.x1 || x >= b.x2) continue;
+        const MiniGlobal m{(const char*)mini + (size_t)s_idx[r] * msz * (dtype == 2 ? 4 : 2), dtype};
+        if (paste_on(m, mh, mw, b, s_sy[r], s_sx[r], y, x)) {
+            lab = s_label[r];
+            break;
+        }
+    }
+    out[p] = lab;
+}
+
+hipError_t launch_detections_to_labels(const int32_t* boxes, const void* mini, int dtype, int mh, int mw, int n,
+                                       int width, int height, int min_area, void* scratch, uint8_t* out,
+                                       uint32_t* areas, hipStream_t s) {
+    static_assert(sizeof(PasteBox) == 4 * sizeof(int32_t), "boxes are [n][4] int32");
+    MaskScratch* sc = (MaskScratch*)scratch;
+    const PasteBox* b = (const PasteBox*)boxes;
+    // the sums are cleared by a kernel, not a memset: a byte memset node of this size, captured in a HIP
+    // graph, filled the scratch with stale words from the second replay on (ROCm 7.2)
+    hipLaunchKernelGGL(k_paste_clear, dim3(1), dim3(kMaxDetections), 0, s, sc);
+    if (n > 0)
+        hipLaunchKernelGGL(k_paste_areas, dim3(kPasteAreaBlocks, n), dim3(256), 0, s, b, mini, dtype, mh, mw, width,
+                           height, sc);
+    hipLaunchKernelGGL(k_mask_decide, dim3(1), dim3(kMaxDetections), 0, s, sc, n, min_area);
+    const int blocks = (width * height + 255) / 256;
+    hipLaunchKernelGGL(k_paste_labels, dim3(blocks), dim3(256), 0, s, b, mini, dtype, mh, mw, n, width, height,
+                       (const MaskScratch*)sc, out, areas);
+    return hipGetLastError();
+}
+
 
 
 // ------------------------------------------------------------------------------------

@@ -24,6 +24,9 @@ utils.py:565-586; norm_boxes / denorm_boxes utils.py:858-889.
 Restated, not bit-identical (no TensorFlow or scikit-image here): image resizing and mask unmolding
 use torch bilinear interpolation (skimage.transform.resize order=1 in the reference); crop_and_resize
 is bilinear sampling with the same sample positions and a zero value for samples outside the map.
+`detect_labels` / `labels_from` skip the masks[H, W, N]: the pixel boxes and the 28x28 masks go to
+semtsdf_detections_to_labels, which thresholds unmold_mask's interpolation in f32 as the reference does
+(`unmold` interpolates in the network's dtype) and applies the dmask.py rule.
 """
 from __future__ import annotations
 
@@ -493,11 +496,16 @@ class MaskRCNN(nn.Module):
         host synchronisation -- N = DETECTION_MAX_INSTANCES rows, the rows past the detections (and
         those unmold_detections drops for zero area) with class 0 and an empty mask, which the dmask.py
         rule (semtsdf_masks_to_labels, areas > 2000) never keeps: for a producer stream."""
+        if not self._calibrated:
+            self.calibrate(image_u8.device, image_u8)
+        det, masks, shape, nwin = self._network(image_u8)
+        return self.unmold(det, masks, (int(image_u8.shape[0]), int(image_u8.shape[1])), shape, nwin, compact)
+
+    def _network(self, image_u8: torch.Tensor):
+        """mold + the inference graph for one image: (det [N, 6], masks [N, classes, 28, 28] f32,
+        the molded image's shape, the normalised window)."""
         cfg = self.config
         dev = image_u8.device
-        if not self._calibrated:
-            self.calibrate(dev, image_u8)
-        H0, W0 = int(image_u8.shape[0]), int(image_u8.shape[1])
         x, window, _ = self.mold(image_u8)
         shape = (cfg.IMAGE_MAX_DIM, cfg.IMAGE_MAX_DIM)
         x = x.to(cfg.DTYPE).contiguous(memory_format=torch.channels_last if CHANNELS_LAST else torch.contiguous_format)
@@ -509,17 +517,25 @@ class MaskRCNN(nn.Module):
         nwin = norm_boxes(np.array(window, dtype=np.float64), shape)
         det = self.detections(rois, probs, bdeltas, tuple(float(v) for v in nwin))
         masks = self.mask_head(self.roi_align(det[:, :4], mfeats, cfg.MASK_POOL_SIZE, shape))
-        return self.unmold(det, masks, (H0, W0), shape, nwin, compact)
+        return det, masks, shape, nwin
 
-    def unmold(self, det, masks, orig_shape, image_shape, nwin, compact=True):
-        """unmold_detections (model.py:2371-2433) + unmold_mask (utils.py:565-586), on the device:
-        the detections (class id > 0) in pixels of the original image and their masks pasted at the
-        boxes (bilinear resize of the 28x28 mask, >= 0.5)."""
+    @torch.no_grad()
+    def detect_labels(self, image_u8: torch.Tensor, min_area: int = 2000, work: torch.Tensor | None = None) -> dict:
+        """One HxWx3 u8 RGB image on the device -> {labels [H, W] u8, rois [N, 4] int32, class_ids [N],
+        scores [N], areas [N]}, N = DETECTION_MAX_INSTANCES fixed rows, all device tensors, no host
+        synchronisation: the network, then `labels_from` (the masks[H, W, N] of `detect` are never made)."""
+        if not self._calibrated:
+            self.calibrate(image_u8.device, image_u8)
+        det, masks, shape, nwin = self._network(image_u8)
+        return self.labels_from(det, masks, (int(image_u8.shape[0]), int(image_u8.shape[1])), shape, nwin, min_area,
+                                work)
+
+    def unmold_boxes(self, d, orig_shape, nwin):
+        """The box arithmetic of unmold_detections (model.py:2395-2423) for detection rows d [n, 6]:
+        (px [n, 4] int32 pixel boxes of the original image, cls [n] int64, ok [n]: class > 0 and a
+        positive pixel area)."""
         H0, W0 = orig_shape
-        dev = det.device
-        # detections come first, zero rows after them
-        n = int((det[:, 4] > 0).sum().item()) if compact else int(det.shape[0])
-        d = det[:n]
+        dev = d.device
         wy1, wx1, wy2, wx2 = (float(v) for v in nwin)
         shift = self._const("shift", (wy1, wx1, wy1, wx1), dev)
         scale = self._const("scale", (wy2 - wy1, wx2 - wx1, wy2 - wy1, wx2 - wx1), dev)
@@ -531,6 +547,50 @@ class MaskRCNN(nn.Module):
                          + self._const("den_shift", (0, 0, 1, 1), dev).double()).to(torch.int32)
         cls = d[:, 4].long()
         ok = ((px[:, 2] - px[:, 0]) * (px[:, 3] - px[:, 1]) > 0) & (cls > 0)
+        return px, cls, ok
+
+    @torch.no_grad()
+    def labels_from(self, det, masks, orig_shape, image_shape, nwin, min_area: int = 2000,
+                    work: torch.Tensor | None = None) -> dict:
+        """The paste stage on given detector outputs, straight to the label map the fusion consumes:
+        unmold_detections' boxes for the fixed rows of det [N, 6] (a dropped row gets a zero box), each
+        row's mask of its own class from masks [N, classes, mh, mw] (fp16, bf16 or f32, passed as it is),
+        then semtsdf_detections_to_labels (include/semtsdf.h: unmold_mask's resize thresholded in f32, and
+        the dmask.py rule).  No host synchronisation; work: a device buffer of
+        masks.detections_to_labels_workspace() bytes (allocated here when None).  Returns {labels [H, W]
+        u8, rois [N, 4] int32, class_ids [N], scores [N], areas [N] int32}."""
+        from .masks import MINI_DTYPES, detections_to_labels_dev, detections_to_labels_workspace
+
+        H0, W0 = orig_shape
+        dev = det.device
+        if dev.type != "cuda":
+            raise RuntimeError("labels_from runs on the GPU (libsemtsdf.so); no CPU fallback")
+        n = int(det.shape[0])
+        px, cls, ok = self.unmold_boxes(det, orig_shape, nwin)
+        px = (px * ok[:, None].to(px.dtype)).contiguous()
+        cls = cls * ok.long()
+        scores = det[:, 5] * ok.float()
+        m = masks[:n][torch.arange(n, device=dev), cls].contiguous()  # [N, mh, mw] of each detection's class
+        code = MINI_DTYPES[str(m.dtype).split(".")[-1]]
+        labels = torch.empty((H0, W0), dtype=torch.uint8, device=dev)
+        areas = torch.empty(n, dtype=torch.int32, device=dev)
+        if work is None:
+            work = torch.empty(detections_to_labels_workspace(n), dtype=torch.uint8, device=dev)
+        detections_to_labels_dev(px.data_ptr(), m.data_ptr(), code, int(m.shape[1]), int(m.shape[2]), n, W0, H0,
+                                 labels.data_ptr(), work.data_ptr(), min_area, areas.data_ptr(),
+                                 stream=torch.cuda.current_stream(dev).cuda_stream)
+        return {"labels": labels, "rois": px, "class_ids": cls.to(torch.int32), "scores": scores, "areas": areas}
+
+    def unmold(self, det, masks, orig_shape, image_shape, nwin, compact=True):
+        """unmold_detections (model.py:2371-2433) + unmold_mask (utils.py:565-586), on the device:
+        the detections (class id > 0) in pixels of the original image and their masks pasted at the
+        boxes (bilinear resize of the 28x28 mask, >= 0.5)."""
+        H0, W0 = orig_shape
+        dev = det.device
+        # detections come first, zero rows after them
+        n = int((det[:, 4] > 0).sum().item()) if compact else int(det.shape[0])
+        d = det[:n]
+        px, cls, ok = self.unmold_boxes(d, orig_shape, nwin)
         if compact:
             px, cls, scores = px[ok], cls[ok], d[ok, 5]
             m = masks[:n][ok]
@@ -566,23 +626,32 @@ class GraphDetector:
     the backbone's and heads' several hundred launches, the NMS kernels and the unmold replayed as one):
     a frame is one copy into the static input and one replay on the current stream; the returned tensors
     are static and are overwritten by the next call.  Calibrate the model first (detect() would do it
-    inside the capture otherwise)."""
+    inside the capture otherwise).  labels=True captures `MaskRCNN.detect_labels` instead (the label map
+    of semtsdf_detections_to_labels in place of the masks), its workspace allocated before the capture."""
 
-    def __init__(self, model: MaskRCNN, image_shape, device, warmup: int = 3):
+    def __init__(self, model: MaskRCNN, image_shape, device, warmup: int = 3, labels: bool = False):
         if not model._calibrated:
             raise RuntimeError("calibrate the model before capturing it")
         self.model = model
         self.inp = torch.zeros(tuple(image_shape), dtype=torch.uint8, device=device)
+        if labels:
+            from .masks import detections_to_labels_workspace
+
+            self.work = torch.empty(detections_to_labels_workspace(model.config.DETECTION_MAX_INSTANCES),
+                                    dtype=torch.uint8, device=device)
+            run = lambda: model.detect_labels(self.inp, work=self.work)  # noqa: E731
+        else:
+            run = lambda: model.detect(self.inp, compact=False)  # noqa: E731
         side = torch.cuda.Stream(device)
         side.wait_stream(torch.cuda.current_stream(device))
         with torch.cuda.stream(side):
             for _ in range(warmup):  # MIOpen's solver choice and the allocator's pools settle first
-                model.detect(self.inp, compact=False)
+                run()
         torch.cuda.current_stream(device).wait_stream(side)
         torch.cuda.synchronize(device)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.out = model.detect(self.inp, compact=False)
+            self.out = run()
 
     def __call__(self, image_u8: torch.Tensor) -> dict:
         self.inp.copy_(image_u8)
