@@ -1474,14 +1474,11 @@ __device__ __forceinline__ void stage_store(const IntegrateArgs& a, const UnitPo
     const VolGeom& g = a.g;
     const unsigned tmask = M.meta & 15u, gmask = (M.meta >> 4) & 15u, hmode = (M.meta >> 8) & 3u,
                    hlab = M.meta >> 16;
-    // the lines with an update stay active together (the flag below is a ballot over a line)
-    const bool line = ((__ballot(tmask != 0u) >> ((int)__lane_id() % LZQ + lane_slot((int)__lane_id()) * kUnitLanes)) &
-                       kLineLanes) != 0ull;
-    if (!line) return;
-    const uint64_t v = O.ub + coff;
     {
         // a brick of the empty-space map changes only where a voxel crossed the threshold:
-        // z-brick j of the unit holds the lanes of z-quads 2j, 2j+1 (lane = zq + 8 y)
+        // z-brick j of the unit holds the lanes of z-quads 2j, 2j+1 (lane = zq + LZQ y).  Every
+        // lane is still here: the marking lane (z-quad j, y 0) marks for the whole brick, also
+        // when its own line has no update and leaves below
         const uint64_t cb = __ballot(O.cross);
         // the struct through the constant address space (scalar loads, lgkmcnt) and its buffers as
         // global pointers: a pointer loaded from memory is generic, and the FLAT atomics and store
@@ -1508,6 +1505,11 @@ __device__ __forceinline__ void stage_store(const IntegrateArgs& a, const UnitPo
             }
         }
     }
+    // the lines with an update stay active together (the flag below is a ballot over a line)
+    const bool line = ((__ballot(tmask != 0u) >> ((int)__lane_id() % LZQ + lane_slot((int)__lane_id()) * kUnitLanes)) &
+                       kLineLanes) != 0ull;
+    if (!line) return;
+    const uint64_t v = O.ub + coff;
     if (!(kProbes && a.debug == 10) && tmask != 0u) {  // 10: timing probe, loads but no sdf/weight stores
         if (!O.skip) st_state(a.b.sdf + v, O.s4);
         st_state(a.b.wt + v, O.w4);

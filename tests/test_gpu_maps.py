@@ -7,10 +7,11 @@ over 0 <= k < cap per axis of max(k, d0(b + s k e))."""
 import numpy as np
 import pytest
 
+from maps_restatement import CAP, numpy_maps  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 KI = (520.9, 521.0, 325.1, 249.7)
-CAP = 16  # kBrickDistCap (SEMTSDF_BRICK_DIST_CAP)
 
 
 @pytest.fixture(scope="module")
@@ -28,46 +29,6 @@ def stream():
 
     st = SyntheticStream(seed=3)
     return st, [st.frame(k) for k in range(5)]
-
-
-def numpy_maps(sdf_xyz: np.ndarray, voxel: float) -> np.ndarray:
-    """Octant words from the definition (dims need not be multiples of 8: partial edge bricks)."""
-    thr = np.float32(voxel) / np.float32(2.0) * np.float32(1.0 + 2.0 ** -16)
-    X, Y, Z = sdf_xyz.shape
-    nb = [(X + 7) // 8, (Y + 7) // 8, (Z + 7) // 8]
-    pad = np.full((nb[0] * 8, nb[1] * 8, nb[2] * 8), np.inf, np.float32)
-    pad[:X, :Y, :Z] = sdf_xyz
-    plain = pad.reshape(nb[0], 8, nb[1], 8, nb[2], 8).min(axis=(1, 3, 5))
-    bmin = plain.copy()
-    for dx in (0, 1):
-        for dy in (0, 1):
-            for dz in (0, 1):
-                sh = np.full_like(plain, np.inf)
-                sh[: nb[0] - dx, : nb[1] - dy, : nb[2] - dz] = plain[dx:, dy:, dz:]
-                bmin = np.minimum(bmin, sh)
-    d0 = np.where(bmin >= thr, CAP, 0).astype(np.int32)
-    words = np.zeros(d0.shape, np.uint64)
-    for o in range(8):
-        d = d0.copy()
-        for a in range(3):
-            s = -1 if (o >> a) & 1 else 1
-            out = d.copy()  # k = 0
-            n = d.shape[a]
-            for k in range(1, CAP):
-                if k >= n:
-                    break
-                sh = np.full_like(d, 1 << 20)
-                src = [slice(None)] * 3
-                dst = [slice(None)] * 3
-                if s > 0:
-                    src[a], dst[a] = slice(k, n), slice(0, n - k)
-                else:
-                    src[a], dst[a] = slice(0, n - k), slice(k, n)
-                sh[tuple(dst)] = d[tuple(src)]
-                out = np.minimum(out, np.maximum(k, sh))
-            d = out
-        words |= d.astype(np.uint64) << np.uint64(8 * o)
-    return words.reshape(-1)
 
 
 @pytest.mark.parametrize("dims", [(96, 96, 96), (120, 88, 136), (64, 160, 40)])
