@@ -263,6 +263,60 @@ int semtsdf_raycast(semtsdf_vol* v, const float s2w[16], const float c[3], int m
 int semtsdf_raycast_dev(semtsdf_vol* v, const float s2w[16], const float c[3], int mode,
                         uint8_t* out_bgr_d, float* out_t_d, void* stream);
 
+/* ---- model maps of a view (no reference counterpart) --------------------------------------------
+ * What the fused model shows along every ray of a view, read-only: hit distance, world position,
+ * surface normal, instance id with its vote count, and a validity byte.  All arithmetic is f32,
+ * every operation rounded on its own unless written fmaf; the view's width and height are the
+ * handle's.  Per pixel (x, y):
+ * Ray and hit: (o, d) as the raycast forms them: p = s2w (x, y, 1) + s2w[:,3] (dot3 then one add),
+ *   r = p - c, d = r * (1 / sqrtf(dot3(r, r))), o = c.  t is the raycast's march and refinement, so
+ *   t equals semtsdf_raycast's out_t bit for bit.  No hit: t = -1, flags = 0, every other output 0.
+ * Point: P[a] = fmaf(t, d[a], o[a]); point = P.
+ * Label and votes: the label render's rule at P without the palette: the trilinear histogram value
+ *   of every bin (clamped sampler, mix(a, b, f) = fmaf(f, b, (1 - f) * a), x then y then z), the
+ *   strict maximum over the bins in ascending order starting from max = 0.0f.  label = its bin
+ *   (0: none), votes = max.
+ * Normal: central differences of trilinear sdf samples one voxel apart.  For each axis a, P+ is P
+ *   with component a replaced by P[a] + voxel[a] and P- by P[a] - voxel[a] (one add each); s+ and s-
+ *   are the clamped trilinear sdf samples there; g[a] = (s+ - s-) / (voxel[a] + voxel[a]), an IEEE
+ *   division.  n2 = dot3(g, g) = fmaf(g2, g2, fmaf(g1, g1, g0 * g0)), inv = 1.0f / sqrtf(n2),
+ *   normal[a] = g[a] * inv.  The normal points from negative to positive sdf, into free space: the
+ *   mesh's convention.
+ * Validity: flags bit 0 (SEMTSDF_MAP_HIT) = hit.  Bit 1 (SEMTSDF_MAP_NORMAL) is set iff all 8
+ *   corners of each of the six samples have weight >= min_weight (the 48 corner indices of the
+ *   clamped sampler, clamped duplicates included) and n2 > 0.0f and n2 is finite.  Otherwise
+ *   normal = (0, 0, 0).
+ * Every pointer of semtsdf_maps_out may be NULL, and an output that is not requested costs nothing:
+ * the histogram is sampled only for label or votes, the six sdf samples and the weights are read
+ * only for normal or flags.  Errors, all decided before any device work: NULL v, s2w, c or out, or
+ * all six pointers NULL: SEMTSDF_ERR_INVALID; a Z-sharded handle: SEMTSDF_ERR_UNSUPPORTED; label or
+ * votes on a volume without SEMTSDF_F_SEMANTIC: SEMTSDF_ERR_STATE.  The launch counts as a render in
+ * the timing (render_ms, n_render).  The volume is not modified; two calls on one state return
+ * identical bytes.
+ * semtsdf_render_maps: host buffers, synchronises; its device scratch (34 B per pixel) is kept on the
+ *   handle after the first call; failing to get it is SEMTSDF_ERR_OOM and the handle stays usable.
+ * semtsdf_render_maps_dev: device buffers, asynchronous on the stream.
+ * semtsdf_pose_camera: the camera whose pixel grid is that of a frame fused with extrinsic E:
+ *   Rt = E[:3,:3]^T, o = -Rt E[:3,3], s2w[:3,:3] = Rt Kinv[:3,:3], s2w[:3,3] = o, last row
+ *   (0, 0, 0, 1), c = o; products and sums accumulated in double (ascending index) and rounded once
+ *   to f32.  The raycast then forms r = (M p + o) - o, so its rays agree with the association's
+ *   (Rt (Kinv p), no origin added and removed) only to about an ulp of |o|: they are not bit-equal. */
+#define SEMTSDF_MAP_HIT 0x1u
+#define SEMTSDF_MAP_NORMAL 0x2u
+typedef struct semtsdf_maps_out { /* each pointer may be NULL; [H*W] or [H*W*3], row-major */
+    float* t;
+    float* point;
+    float* normal;
+    uint8_t* label;
+    float* votes;
+    uint8_t* flags;
+} semtsdf_maps_out;
+int semtsdf_render_maps(semtsdf_vol* v, const float s2w[16], const float c[3], int32_t min_weight,
+                        const semtsdf_maps_out* out_host, void* stream);
+int semtsdf_render_maps_dev(semtsdf_vol* v, const float s2w[16], const float c[3], int32_t min_weight,
+                            const semtsdf_maps_out* out_dev, void* stream);
+int semtsdf_pose_camera(const float Kinv[16], const float E[16], float s2w[16], float c[3]);
+
 /* ---- Z-sharded raycast (replaces the single-GPU back_proj_kernel
  * tsdf.cu:72-135 and show_tsdf_kernel viewer.cu:17-86 when the volume is split across GPUs)
  * Every shard of a group runs the same call sequence.  Between calls the host exchanges

@@ -110,6 +110,7 @@ struct semtsdf_vol {
     uint8_t* palette_d = nullptr;
     uint8_t* render_d = nullptr;
     float* render_t_d = nullptr;
+    uint8_t* maps_d = nullptr;     // semtsdf_render_maps: the six maps back to back (34 B per pixel)
     unsigned long long* counters_d = nullptr;
     IntegrateRare* rare_d = nullptr;  // the integrate's rare-path fields (IntegrateArgs::rare)
     float* rcp_table_d = nullptr;    // RN(1/n), n = 1..kRcpTable
@@ -175,7 +176,7 @@ int dev_alloc(semtsdf_vol* v, void** p, size_t bytes) {
 void free_all(semtsdf_vol* v) {
     void* ptrs[] = {v->b.sdf, v->b.wt, v->b.bplain, v->b.boct, v->b.botmp, v->b.bdirty, v->b.dlist, v->b.sflag, v->b.color, v->b.hist, v->b.hmask, v->b.cls, v->b.cls_cnt, v->depth_d, v->rgb_d,
                     v->mask_d, v->cls_d, v->tables_d, v->decision_d,
-                    v->num_objs_d, v->probs_d, v->box_d, v->palette_d, v->render_d, v->render_t_d,
+                    v->num_objs_d, v->probs_d, v->box_d, v->palette_d, v->render_d, v->render_t_d, v->maps_d,
                     v->counters_d, v->ray_state_d, v->rcp_table_d, v->wtrace_d, v->exact_d, v->px.bits, v->px.p, v->tile_cost_d, v->tile_perm_d, v->rare_d};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
@@ -1808,6 +1809,99 @@ int semtsdf_raycast_dev(semtsdf_vol* v, const float s2w[16], const float c[3], i
                         float* out_t_d, void* stream) {
     if (!v || !s2w || !c || !out_bgr_d) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
     return raycast_impl(v, s2w, c, mode, out_bgr_d, out_t_d, pick(v, stream));
+}
+
+int semtsdf_pose_camera(const float Kinv[16], const float E[16], float s2w[16], float c[3]) {
+    if (!Kinv || !E || !s2w || !c) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
+    // Rt = E[:3,:3]^T, o = -Rt E[:3,3], s2w = [Rt Kinv[:3,:3] | o]: sums of double products, rounded once
+    float o[3];
+    for (int i = 0; i < 3; ++i) {
+        double acc = 0;
+        for (int k = 0; k < 3; ++k) acc += (double)E[k * 4 + i] * (double)E[k * 4 + 3];
+        o[i] = (float)(-acc);
+    }
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) {
+            double acc = 0;
+            for (int k = 0; k < 3; ++k) acc += (double)E[k * 4 + i] * (double)Kinv[k * 4 + j];
+            s2w[i * 4 + j] = (float)acc;
+        }
+        s2w[i * 4 + 3] = o[i];
+        c[i] = o[i];
+    }
+    s2w[12] = s2w[13] = s2w[14] = 0.0f;
+    s2w[15] = 1.0f;
+    return SEMTSDF_OK;
+}
+
+// Argument checks of the model maps, all before any device work.
+static int maps_check(semtsdf_vol* v, const float* s2w, const float* c, const semtsdf_maps_out* out) {
+    if (!v || !s2w || !c || !out) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
+    if (!out->t && !out->point && !out->normal && !out->label && !out->votes && !out->flags)
+        return fail(SEMTSDF_ERR_INVALID, "NULL outputs: no map requested");
+    if (v->p.z_nshards != 1) return fail(SEMTSDF_ERR_UNSUPPORTED, "model maps on a Z-sharded handle are not supported yet");
+    if ((out->label || out->votes) && !(v->p.flags & SEMTSDF_F_SEMANTIC))
+        return fail(SEMTSDF_ERR_STATE, "label and votes maps need a SEMANTIC volume");
+    return SEMTSDF_OK;
+}
+
+static int maps_impl(semtsdf_vol* v, const float s2w[16], const float c[3], int32_t min_weight,
+                     const semtsdf_maps_out& out_d, hipStream_t s) {
+    MapsArgs a{};
+    a.g = v->g;
+    for (int i = 0; i < 12; ++i) a.cam.s2w[i] = s2w[i];
+    a.cam.o[0] = c[0]; a.cam.o[1] = c[1]; a.cam.o[2] = c[2];
+    a.cam.use_s2w = 1;
+    a.width = v->p.width;
+    a.height = v->p.height;
+    a.min_weight = min_weight;
+    a.t = out_d.t; a.point = out_d.point; a.normal = out_d.normal;
+    a.label = out_d.label; a.votes = out_d.votes; a.flags = out_d.flags;
+    EventPair ep;
+    if (int rc = ensure_maps(v, s)) return rc;
+    a.b = v->b;  // the map buffers as ensure_maps left them
+    timing_begin(v, v->ev_render, s, &ep);
+    HIPC(launch_model_maps(a, s));
+    timing_end(v, v->ev_render, s, &ep);
+    v->n_render++;
+    return SEMTSDF_OK;
+}
+
+int semtsdf_render_maps_dev(semtsdf_vol* v, const float s2w[16], const float c[3], int32_t min_weight,
+                            const semtsdf_maps_out* out_dev, void* stream) {
+    if (int rc = maps_check(v, s2w, c, out_dev)) return rc;
+    return maps_impl(v, s2w, c, min_weight, *out_dev, pick(v, stream));
+}
+
+int semtsdf_render_maps(semtsdf_vol* v, const float s2w[16], const float c[3], int32_t min_weight,
+                        const semtsdf_maps_out* out_host, void* stream) {
+    if (int rc = maps_check(v, s2w, c, out_host)) return rc;
+    HIPC(hipSetDevice(v->device));
+    hipStream_t s = pick(v, stream);
+    const size_t n = npx(v);
+    if (!v->maps_d) {  // t, point, normal, votes (4-B aligned), then label and flags
+        if (int rc = dev_alloc(v, (void**)&v->maps_d, n * 34)) {
+            v->maps_d = nullptr;
+            return rc;
+        }
+    }
+    float* f = reinterpret_cast<float*>(v->maps_d);
+    semtsdf_maps_out d{};
+    d.t = out_host->t ? f : nullptr;
+    d.point = out_host->point ? f + n : nullptr;
+    d.normal = out_host->normal ? f + n * 4 : nullptr;
+    d.votes = out_host->votes ? f + n * 7 : nullptr;
+    d.label = out_host->label ? v->maps_d + n * 32 : nullptr;
+    d.flags = out_host->flags ? v->maps_d + n * 33 : nullptr;
+    if (int rc = maps_impl(v, s2w, c, min_weight, d, s)) return rc;
+    if (d.t) HIPC(hipMemcpyAsync(out_host->t, d.t, n * 4, hipMemcpyDeviceToHost, s));
+    if (d.point) HIPC(hipMemcpyAsync(out_host->point, d.point, n * 12, hipMemcpyDeviceToHost, s));
+    if (d.normal) HIPC(hipMemcpyAsync(out_host->normal, d.normal, n * 12, hipMemcpyDeviceToHost, s));
+    if (d.votes) HIPC(hipMemcpyAsync(out_host->votes, d.votes, n * 4, hipMemcpyDeviceToHost, s));
+    if (d.label) HIPC(hipMemcpyAsync(out_host->label, d.label, n, hipMemcpyDeviceToHost, s));
+    if (d.flags) HIPC(hipMemcpyAsync(out_host->flags, d.flags, n, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    return SEMTSDF_OK;
 }
 
 // A 4-byte per-voxel array between the reference layout (rows of lz planes, dense) and the

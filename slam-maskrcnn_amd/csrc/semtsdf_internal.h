@@ -276,6 +276,21 @@ struct RenderArgs {
     int row0, row1;          // instrumentation (SEMTSDF_RENDER_ROWS): only 16-px tile rows [row0, row1)
 };
 
+// Model maps of a view (k_model_maps): the outputs of semtsdf_maps_out, each nullable.
+struct MapsArgs {
+    VolGeom g;
+    VolBufs b;
+    MarchCamera cam;
+    int width, height;
+    int min_weight;
+    float* t;          // [npx]
+    float* point;      // [npx][3]
+    float* normal;     // [npx][3]
+    uint8_t* label;    // [npx]
+    float* votes;      // [npx]
+    uint8_t* flags;    // [npx]
+};
+
 // Z-sharded raycast protocol (k_shard_* in semtsdf_kernels.hip): per-pixel march state.
 struct ShardRayState {
     int* k;      // global coarse event index, -1 = miss
@@ -358,6 +373,7 @@ hipError_t launch_libm_eval(int fn, const float* x, float* y, size_t n, hipStrea
 hipError_t launch_first_frame_objs(const AssocTables* t, int* num_objs_dev, hipStream_t s);
 hipError_t launch_relabel(uint8_t* mask, int npx, const AssocDecision* d, hipStream_t s);
 hipError_t launch_render(const RenderArgs& a, hipStream_t s);
+hipError_t launch_model_maps(const MapsArgs& a, hipStream_t s);
 hipError_t launch_march_fused(const AssocArgs& aa, const RenderArgs& ra, hipStream_t s);
 hipError_t launch_copy_host(const void* src, void* dst, size_t n16, hipStream_t s);
 // chunk [v0, v0+nv) of the bin-major histogram <-> voxel-major [nv][32] staging buffer

@@ -3448,6 +3448,117 @@ hipError_t launch_render(const RenderArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------
+// model maps (semtsdf_render_maps, include/semtsdf.h): the march of a render, then per hit
+// the position, the unmapped argmax instance with its vote count, and the central-difference
+// normal of the sdf with its validity.  No reference counterpart.
+// ------------------------------------------------------------------------------------
+// One trilinear sdf sample of the normal's stencil at (px, py, pz); *wmin takes the minimum
+// with the weights of the sample's 8 corners (the corners tri_coord gives, clamped
+// duplicates included).
+__device__ __forceinline__ float maps_sample(const VolGeom& g, const VolBufs& b, float px, float py, float pz,
+                                             int* wmin) {
+    const Tri tr = tri_setup<false>(g, px, py, pz);
+    const int32_t* q = b.wt + tr.i000;
+    const int w0 = min(min(q[0], q[tr.dz]), min(q[tr.dy], q[tr.dy + tr.dz]));
+    const int w1 = min(min(q[tr.dx], q[tr.dx + tr.dz]), min(q[tr.dx + tr.dy], q[tr.dx + tr.dy + tr.dz]));
+    *wmin = min(*wmin, min(w0, w1));
+    return tri_eval(b.sdf, tr);
+}
+
+// LABEL: label or votes requested (the histogram samples); NORMAL: normal or flags requested
+// (the six sdf samples and the weight test).  Neither: the march, t and the point alone, the
+// registers of k_render.  Which pointers of a group are written is a wave-uniform test of
+// the kernel arguments.
+template <bool LABEL, bool NORMAL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SEMTSDF_MARCH_WPE))) void k_model_maps(MapsArgs a) {
+    const int x = (int)blockIdx.x * 16 + (int)(threadIdx.x & 15);
+    const int y = (int)blockIdx.y * 16 + (int)(threadIdx.x >> 4);
+    if (x >= a.width || y >= a.height) return;
+    const size_t px = (size_t)y * a.width + x;
+    float ox, oy, oz, dx, dy, dz, t;
+    ray_render(a.cam, x, y, &ox, &oy, &oz, &dx, &dy, &dz);
+    float th = -1.0f, P[3] = {0.0f, 0.0f, 0.0f}, n[3] = {0.0f, 0.0f, 0.0f}, votes = 0.0f;
+    int obj = 0;
+    unsigned fl = 0;
+    if (march_ray(a.g, a.b, ox, oy, oz, dx, dy, dz, &t, nullptr)) {
+        th = t;
+        fl = 1u;  // SEMTSDF_MAP_HIT
+        P[0] = fmaf(t, dx, ox);
+        P[1] = fmaf(t, dy, oy);
+        P[2] = fmaf(t, dz, oz);
+        if (LABEL) {  // shade_hit mode 0 without the palette
+            const Tri tr = tri_setup<false>(a.g, P[0], P[1], P[2]);
+            unsigned bins = tri_bins(a.b.hmask, tr);  // bins outside the mask are 0: never a strict max
+            while (bins) {
+                const int k = __ffs((int)bins) - 1;
+                bins &= bins - 1u;
+                const float c = tri_eval(a.b.hist + (uint64_t)k * a.g.nvox, tr);
+                if (c > votes) { votes = c; obj = k; }
+            }
+        }
+        if (NORMAL) {
+            int wmin = INT_MAX;
+            float g0 = 0.0f, g1 = 0.0f, g2 = 0.0f;
+            // one axis at a time (a loop, not unrolled): the 32 loads of an axis in flight, not
+            // all 96, which keeps the kernel at the march's register count (4 waves per SIMD)
+#pragma unroll 1
+            for (int ax = 0; ax < 3; ++ax) {
+                const bool ax0 = ax == 0, ax1 = ax == 1, ax2 = ax == 2;
+                const float v = ax0 ? a.g.voxel[0] : ax1 ? a.g.voxel[1] : a.g.voxel[2];
+                const float pa = ax0 ? P[0] : ax1 ? P[1] : P[2];
+                const float hi = pa + v, lo = pa - v;
+                const float sp = maps_sample(a.g, a.b, ax0 ? hi : P[0], ax1 ? hi : P[1], ax2 ? hi : P[2], &wmin);
+                const float sm = maps_sample(a.g, a.b, ax0 ? lo : P[0], ax1 ? lo : P[1], ax2 ? lo : P[2], &wmin);
+                const float d = (sp - sm) / (v + v);
+                g0 = ax0 ? d : g0;
+                g1 = ax1 ? d : g1;
+                g2 = ax2 ? d : g2;
+            }
+            const float n2 = dot3(g0, g1, g2, g0, g1, g2);
+            if (wmin >= a.min_weight && n2 > 0.0f && n2 < __builtin_inff()) {
+                const float inv = 1.0f / sqrtf(n2);
+                n[0] = g0 * inv;
+                n[1] = g1 * inv;
+                n[2] = g2 * inv;
+                fl |= 2u;  // SEMTSDF_MAP_NORMAL
+            }
+        }
+    }
+    if (a.t) a.t[px] = th;
+    if (a.point) {
+        a.point[px * 3 + 0] = P[0];
+        a.point[px * 3 + 1] = P[1];
+        a.point[px * 3 + 2] = P[2];
+    }
+    if (LABEL) {
+        if (a.label) a.label[px] = (uint8_t)obj;
+        if (a.votes) a.votes[px] = votes;
+    }
+    if (NORMAL) {
+        if (a.normal) {
+            a.normal[px * 3 + 0] = n[0];
+            a.normal[px * 3 + 1] = n[1];
+            a.normal[px * 3 + 2] = n[2];
+        }
+        if (a.flags) a.flags[px] = (uint8_t)fl;
+    }
+}
+
+hipError_t launch_model_maps(const MapsArgs& a, hipStream_t s) {
+    const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
+    const bool lab = a.label || a.votes, nor = a.normal || a.flags;
+    if (lab && nor)
+        hipLaunchKernelGGL((k_model_maps<true, true>), grid, dim3(256), 0, s, a);
+    else if (lab)
+        hipLaunchKernelGGL((k_model_maps<true, false>), grid, dim3(256), 0, s, a);
+    else if (nor)
+        hipLaunchKernelGGL((k_model_maps<false, true>), grid, dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_model_maps<false, false>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
 // Z-sharded raycast.  The march of march_ray is sequential along the ray
 // (sticky quarter step, refinement from the previous sample), so it is split into steps
 // that every rank of the group runs on its own planes, with an all-gather of one 8-byte

@@ -11,6 +11,8 @@ from .config import Configuration, FusionConfig
 from .export import (export_surface, extract_mesh, merge_meshes, read_mesh_ply, read_ply, write_mesh_ply,
                      write_ply)
 from .instances import find_duplicates, instance_stats, merge_instance_stats, plan_remap
+from . import maps
+from .maps import pose_camera, shade_normals, z_depth
 from .tsdf import TSDF
 from .volume import DeviceBuffer, Volume, default_params, orbit_camera, place_from_frame
 
@@ -18,4 +20,5 @@ __all__ = ["TSDF", "Volume", "DeviceBuffer", "Configuration", "FusionConfig", "S
            "default_params", "place_from_frame", "orbit_camera", "_lib", "export_surface", "write_ply", "read_ply",
            "extract_mesh", "merge_meshes", "write_mesh_ply", "read_mesh_ply",
            "instance_stats", "merge_instance_stats", "find_duplicates", "plan_remap",
+           "maps", "pose_camera", "z_depth", "shade_normals",
            "RENDER_LABEL", "RENDER_COLOR", "RAY_ASSOC", "PLACE_SFM", "PLACE_PYTHON"]

@@ -116,6 +116,17 @@ class Instance(C.Structure):
                 ("rgb_sum", C.c_uint64 * 3), ("min", C.c_uint32 * 3), ("max", C.c_uint32 * 3)]
 
 
+class MapsOut(C.Structure):
+    """semtsdf_maps_out: one pointer per map, NULL where the map is not requested."""
+    _fields_ = [("t", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("label", C.c_void_p),
+                ("votes", C.c_void_p), ("flags", C.c_void_p)]
+
+
+MAP_HIT = 0x1
+MAP_NORMAL = 0x2
+MAP_NAMES = ("t", "point", "normal", "label", "votes", "flags")
+
+
 class Timing(C.Structure):
     _fields_ = [
         ("integrate_ms", C.c_double),
@@ -183,6 +194,9 @@ SIGNATURES = {
     "semtsdf_orbit_camera": (_I, [_P, _F, _F, _P, _P]),
     "semtsdf_raycast": (_I, [_P, _P, _P, _I, _P, _P, _P]),
     "semtsdf_raycast_dev": (_I, [_P, _P, _P, _I, _P, _P, _P]),
+    "semtsdf_render_maps": (_I, [_P, _P, _P, C.c_int32, C.POINTER(MapsOut), _P]),
+    "semtsdf_render_maps_dev": (_I, [_P, _P, _P, C.c_int32, C.POINTER(MapsOut), _P]),
+    "semtsdf_pose_camera": (_I, [_P, _P, _P, _P]),
     "semtsdf_shard_ray_begin": (_I, [_P, _I, _P, _P, _I, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "semtsdf_shard_ray_step": (_I, [_P, _I, _P, _P, _P]),
     "semtsdf_shard_render_finish": (_I, [_P, _P, _P, _P, _P]),

@@ -27,6 +27,8 @@ def orbit_views(vol, kinv, dist: float, n: int, mode: str = "label", step: float
     (viewer.cu:81-83 writes B, G, R).  The raycast of view k+1 is queued before view k is
     encoded, so the GPU does not wait for the host's PNG encoding.
     Returns the list of written paths (out_dir) or of images (no out_dir, no callback)."""
+    if mode == "normal":
+        return _orbit_normals(vol, kinv, dist, n, step, start, out_dir, callback)
     m = L.RENDER_LABEL if mode == "label" else L.RENDER_COLOR
     H, W = vol.H, vol.W
     buf = DeviceBuffer(W * H * 3)
@@ -59,6 +61,30 @@ def orbit_views(vol, kinv, dist: float, n: int, mode: str = "label", step: float
     return out
 
 
+def _orbit_normals(vol, kinv, dist, n, step, start, out_dir, callback):
+    """orbit_views in mode "normal": every view is the shaded surface (semtsdf.maps.shade_normals)
+    of the view's model maps."""
+    from .maps import shade_normals
+
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+    out = []
+    for k, a in enumerate(start + a for a in orbit_angle_sequence(n, step)):
+        s2w, c = orbit_camera(kinv, a, dist)
+        img = shade_normals(vol.render_maps(s2w, c, want=("point", "normal", "flags")), c)
+        if callback is not None:
+            callback(k, a, img)
+        if out_dir:
+            from PIL import Image
+
+            path = os.path.join(out_dir, f"view_{k:05d}.png")
+            Image.fromarray(img).save(path)  # grey: B = G = R
+            out.append(path)
+        elif callback is None:
+            out.append(img)
+    return out
+
+
 def main(argv=None):
     from .tsdf import TSDF
 
@@ -66,7 +92,7 @@ def main(argv=None):
     ap.add_argument("checkpoint")
     ap.add_argument("out_dir")
     ap.add_argument("--views", type=int, default=60)
-    ap.add_argument("--mode", choices=["label", "color"], default="label")
+    ap.add_argument("--mode", choices=["label", "color", "normal"], default="label")
     ap.add_argument("--step", type=float, default=0.01)
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)

@@ -239,7 +239,28 @@ class TSDF:
     def render(self, angle: float, mode: str = "label", dist: float | None = None):
         """Viewer::show_tsdf (viewer.cu:137-179) without the window: BGR u8 image."""
         s2w, c = orbit_camera(self.intrinsic_inv, angle, self.mean_depth if dist is None else dist)
+        if mode == "normal":  # the shaded surface: semtsdf.maps.shade_normals of the view's maps
+            from .maps import shade_normals
+
+            return shade_normals(self.vol.render_maps(s2w, c, want=("point", "normal", "flags")), c)
         return self.vol.raycast(s2w, c, L.RENDER_LABEL if mode == "label" else L.RENDER_COLOR)
+
+    def model_maps(self, extrinsic=None, angle: float | None = None, dist: float | None = None, min_weight: int = 1):
+        """The model maps (Volume.render_maps: t, point, normal, flags, and label, votes of a semantic
+        volume) of a frame pose -- `extrinsic` as parse_frame takes it, through
+        semtsdf.maps.pose_camera, so the maps share the frame's pixel grid -- or of the orbit view
+        at `angle` (and `dist`, default the mean depth)."""
+        from .maps import pose_camera
+
+        if (extrinsic is None) == (angle is None):
+            raise ValueError("give either extrinsic or angle")
+        if extrinsic is not None:
+            s2w, c = pose_camera(self.intrinsic_inv, P.relative_pose(extrinsic, self.init_extrinsic_inv))
+        else:
+            s2w, c = orbit_camera(self.intrinsic_inv, angle, self.mean_depth if dist is None else dist)
+        sem = bool(self.vol.params.flags & L.F_SEMANTIC)
+        want = tuple(n for n in L.MAP_NAMES if sem or n not in ("label", "votes"))
+        return self.vol.render_maps(s2w, c, min_weight, want)
 
     def orbit(self, n: int, out_dir: str | None = None, mode: str = "label", step: float = 0.01, callback=None):
         """The reference's view loop (kernel.cpp:101-107: angle += 0.01 per view at the mean

@@ -237,6 +237,35 @@ class Volume:
         L.check(L.load().semtsdf_raycast_dev(self._h, L.ptr(s), L.ptr(cc), int(mode), C.c_void_p(out_ptr),
                                              C.c_void_p(t_ptr) if t_ptr else None, stream))
 
+    # ---- model maps
+    def render_maps(self, s2w, c, min_weight: int = 1, want=L.MAP_NAMES) -> dict:
+        """The model maps of a view (semtsdf_render_maps): a dict of the maps named in `want`,
+        NumPy arrays [H, W] (t, votes f32; label, flags u8) or [H, W, 3] (point, normal f32)."""
+        from .maps import MAP_LAYOUT, maps_out
+
+        want = (want,) if isinstance(want, str) else tuple(want)
+        out = {}
+        for name in want:
+            if name not in MAP_LAYOUT:
+                raise ValueError(f"unknown map {name!r} (one of {', '.join(L.MAP_NAMES)})")
+            dt, ch = MAP_LAYOUT[name]
+            out[name] = np.zeros((self.H, self.W) + ((ch,) if ch > 1 else ()), dt)
+        o = maps_out(want, out)
+        s = L.f32(s2w, 16)
+        cc = L.f32(c, 3)
+        L.check(L.load().semtsdf_render_maps(self._h, L.ptr(s), L.ptr(cc), int(min_weight), C.byref(o), None))
+        return out
+
+    def render_maps_dev(self, s2w, c, min_weight: int = 1, stream=None, **pointers):
+        """render_maps into device buffers, asynchronous on `stream`: one raw device pointer per
+        requested map, by name (t=..., point=..., normal=..., label=..., votes=..., flags=...)."""
+        from .maps import maps_out
+
+        o = maps_out([k for k, p in pointers.items() if p], pointers)
+        s = L.f32(s2w, 16)
+        cc = L.f32(c, 3)
+        L.check(L.load().semtsdf_render_maps_dev(self._h, L.ptr(s), L.ptr(cc), int(min_weight), C.byref(o), stream))
+
     # ---- state transfer (reference layouts)
     def download(self, sdf=True, wt=True, color=True, hist=False, cls=False):
         n = self.nvox
