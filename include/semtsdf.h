@@ -317,6 +317,83 @@ int semtsdf_render_maps_dev(semtsdf_vol* v, const float s2w[16], const float c[3
                             const semtsdf_maps_out* out_dev, void* stream);
 int semtsdf_pose_camera(const float Kinv[16], const float E[16], float s2w[16], float c[3]);
 
+/* ---- camera tracking: frame maps and the point-to-plane system (no reference counterpart) --------
+ * What one iteration of frame-to-model ICP needs from the device: the camera-space vertex and normal
+ * of every depth pixel (the frame-side counterpart of the model maps), and the normal equations of
+ * the point-to-plane error between those and the model maps of a reference view, as order-free
+ * fixed-point sums.  The 6 x 6 solve and the pose update are the host's (semtsdf/track.py).  All
+ * arithmetic is f32, every operation rounded on its own, with dot3(a, b) = fmaf(a2, b2, fmaf(a1, b1,
+ * a0 * b0)) as in the model maps and cross(a, b) = (a1 * b2 - a2 * b1, a2 * b0 - a0 * b2, a0 * b1 -
+ * a1 * b0): two rounded products and one subtraction per component, no fmaf.  Width W, height H, K,
+ * Kinv and depth_scale are the handle's; neither call reads or modifies the volume.
+ *
+ * Frame maps.  Per pixel (x, y) with raw depth D (u16):
+ * Vertex: z = (float)D / depth_scale (an IEEE division: the value the integrate's pixel record
+ *   holds), r[a] = dot3(Kinv[a][0..2], ((float)x, (float)y, 1.0f)), V[a] = r[a] * z.  flags bit 0 =
+ *   (D != 0); where D == 0, V = (+0, +0, +0).
+ * Normal: A = V(x, y + 1) - V, B = V(x + 1, y) - V (componentwise), g = cross(A, B), n2 = dot3(g, g),
+ *   inv = 1.0f / sqrtf(n2), n[a] = g[a] * inv.  It points towards the camera, into free space: the
+ *   model maps' convention.  flags bit 1 is set iff x + 1 < W and y + 1 < H, the three depths are
+ *   nonzero, n2 > 0.0f and n2 is finite; otherwise n = (+0, +0, +0).
+ * No smoothing and no pyramid: the gates below reject depth edges.  Every output pointer may be NULL
+ * (all three NULL: SEMTSDF_ERR_INVALID); an output requested alone equals that of the full call.
+ * semtsdf_frame_maps: host buffers, synchronises.  semtsdf_frame_maps_dev: device buffers,
+ * asynchronous on the stream.
+ *
+ * The system of one iteration.  Inputs (semtsdf_icp_in): the frame maps above and the model maps
+ * point, normal, flags of a reference view as semtsdf_render_maps wrote them for
+ * semtsdf_pose_camera(Kinv, E_ref); E_ref; E_cur, the current estimate (volume to camera, the
+ * integrate's convention); dist_max (metres), cos_min, stride.  On the host, before the launch:
+ *   Rt = E_cur[:3,:3]^T and o = -Rt E_cur[:3,3] exactly as semtsdf_pose_camera forms them (sums of
+ *   double products in ascending index, rounded once to f32); dmax2 = dist_max * dist_max (one f32
+ *   product).
+ * Every frame pixel (x, y) with x % stride == 0, y % stride == 0 and frame flags & 3 == 3 is visited
+ * and falls into exactly one of four classes, by these steps in order (V, n: its frame maps):
+ *  1. Pw[a] = dot3(Rt[a], V) + o[a];  Nw[a] = dot3(Rt[a], n).
+ *  2. q[a] = dot3(E_ref[a][0..2], Pw) + E_ref[a][3];  s[a] = dot3(K[a][0..2], q).  Class none if
+ *     q[2] <= 0.  u = floorf(s[0] / s[2] + 0.5f), v = floorf(s[1] / s[2] + 0.5f) (IEEE divisions).
+ *     Class none unless 0 <= u < W and 0 <= v < H (compared as floats, so a NaN is off the image) and
+ *     the model flags at (u, v) have both SEMTSDF_MAP_HIT and SEMTSDF_MAP_NORMAL.  Pm, Nm: the model
+ *     point and normal at (u, v).
+ *  3. d[a] = Pm[a] - Pw[a].  Class far if dot3(d, d) > dmax2.
+ *  4. Class angle if dot3(Nm, Nw) < cos_min.
+ *  5. r = dot3(Nm, d);  J = (cross(Pw, Nm), Nm), six values.  Class none unless every |J[i]| < 32 (a
+ *     NaN is out of range): the range gate that bounds the sums below.
+ *  6. Inlier.  Each product J[i] * J[j] (i <= j), J[i] * r and r * r is formed in double (exact for f32
+ *     factors), multiplied by 2^32 (exact), rounded to nearest-even to int64 and added to its word.
+ * Output: 32 int64 words.  0..20: the upper triangle of J^T J, row-major ((0,0), (0,1), .. (0,5),
+ * (1,1), .. (5,5)); 21..26: J^T r; 27: sum of r^2; 28: inliers; 29: far; 30: angle; 31: none.  Words
+ * 28..31 are plain counts and sum to the number of pixels visited.  The rows describe the twist
+ * xi = (omega, v) of the volume frame that minimises sum (r - J xi)^2: solve (J^T J) xi = J^T r and
+ * move the camera by C2W <- exp(xi) C2W.  Each term is below 2^10 * 2^32 = 2^42 in magnitude and
+ * W * H <= 2^19, so no sum reaches 2^61; integer sums do not depend on order, so the words are the
+ * same on every run and for every reduction shape.
+ * Errors, all decided before any device work: a NULL argument or input pointer, W * H > 2^19,
+ * stride < 1, dist_max outside (0, 1] or cos_min outside [-1, 1] (a NaN is outside):
+ * SEMTSDF_ERR_INVALID; a Z-sharded handle: SEMTSDF_ERR_UNSUPPORTED (both calls, as for the maps).
+ * semtsdf_icp_system_dev: device pointers in `in_dev` and `words_dev`; zeroes the words on the
+ *   stream, then one launch; asynchronous, nothing is read back.
+ * semtsdf_icp_system: host pointers; uploads the six maps, runs the same launch and synchronises.
+ * The host variants keep their device scratch (52 B per pixel) on the handle after the first call. */
+typedef struct semtsdf_icp_in { /* [H*W] or [H*W*3], row-major */
+    const float* vertex;     /* frame maps */
+    const float* normal;
+    const uint8_t* flags;
+    const float* m_point;    /* model maps of the reference view */
+    const float* m_normal;
+    const uint8_t* m_flags;
+} semtsdf_icp_in;
+#define SEMTSDF_ICP_WORDS 32
+int semtsdf_frame_maps(semtsdf_vol* v, const uint16_t* depth, float* vertex, float* normal, uint8_t* flags,
+                       void* stream);
+int semtsdf_frame_maps_dev(semtsdf_vol* v, const uint16_t* depth_d, float* vertex_d, float* normal_d,
+                           uint8_t* flags_d, void* stream);
+int semtsdf_icp_system(semtsdf_vol* v, const semtsdf_icp_in* in_host, const float E_ref[16], const float E_cur[16],
+                       float dist_max, float cos_min, int32_t stride, int64_t* words_host, void* stream);
+int semtsdf_icp_system_dev(semtsdf_vol* v, const semtsdf_icp_in* in_dev, const float E_ref[16],
+                           const float E_cur[16], float dist_max, float cos_min, int32_t stride, int64_t* words_dev,
+                           void* stream);
+
 /* ---- Z-sharded raycast (replaces the single-GPU back_proj_kernel
  * tsdf.cu:72-135 and show_tsdf_kernel viewer.cu:17-86 when the volume is split across GPUs)
  * Every shard of a group runs the same call sequence.  Between calls the host exchanges

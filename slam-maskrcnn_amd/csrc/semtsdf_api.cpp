@@ -111,6 +111,7 @@ struct semtsdf_vol {
     uint8_t* render_d = nullptr;
     float* render_t_d = nullptr;
     uint8_t* maps_d = nullptr;     // semtsdf_render_maps: the six maps back to back (34 B per pixel)
+    uint8_t* track_d = nullptr;    // semtsdf_frame_maps / semtsdf_icp_system: host-variant scratch (52 B per pixel)
     unsigned long long* counters_d = nullptr;
     IntegrateRare* rare_d = nullptr;  // the integrate's rare-path fields (IntegrateArgs::rare)
     float* rcp_table_d = nullptr;    // RN(1/n), n = 1..kRcpTable
@@ -176,7 +177,7 @@ int dev_alloc(semtsdf_vol* v, void** p, size_t bytes) {
 void free_all(semtsdf_vol* v) {
     void* ptrs[] = {v->b.sdf, v->b.wt, v->b.bplain, v->b.boct, v->b.botmp, v->b.bdirty, v->b.dlist, v->b.sflag, v->b.color, v->b.hist, v->b.hmask, v->b.cls, v->b.cls_cnt, v->depth_d, v->rgb_d,
                     v->mask_d, v->cls_d, v->tables_d, v->decision_d,
-                    v->num_objs_d, v->probs_d, v->box_d, v->palette_d, v->render_d, v->render_t_d, v->maps_d,
+                    v->num_objs_d, v->probs_d, v->box_d, v->palette_d, v->render_d, v->render_t_d, v->maps_d, v->track_d,
                     v->counters_d, v->ray_state_d, v->rcp_table_d, v->wtrace_d, v->exact_d, v->px.bits, v->px.p, v->tile_cost_d, v->tile_perm_d, v->rare_d};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
@@ -1900,6 +1901,145 @@ int semtsdf_render_maps(semtsdf_vol* v, const float s2w[16], const float c[3], i
     if (d.votes) HIPC(hipMemcpyAsync(out_host->votes, d.votes, n * 4, hipMemcpyDeviceToHost, s));
     if (d.label) HIPC(hipMemcpyAsync(out_host->label, d.label, n, hipMemcpyDeviceToHost, s));
     if (d.flags) HIPC(hipMemcpyAsync(out_host->flags, d.flags, n, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    return SEMTSDF_OK;
+}
+
+// ---- camera tracking: frame maps and the point-to-plane system ---------------------------------
+// Device scratch of the host-pointer variants, 52 B per pixel + the words: the 4-B aligned arrays
+// first (frame vertex, normal; model point, normal; the words), then the two flag maps and the depth.
+static int track_scratch(semtsdf_vol* v) {
+    if (v->track_d) return SEMTSDF_OK;
+    if (int rc = dev_alloc(v, (void**)&v->track_d, npx(v) * 52 + kIcpWords * 8)) {
+        v->track_d = nullptr;
+        return rc;
+    }
+    return SEMTSDF_OK;
+}
+
+static int frame_maps_check(semtsdf_vol* v, const uint16_t* depth, float* vertex, float* normal, uint8_t* flags) {
+    if (!v || !depth) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
+    if (!vertex && !normal && !flags) return fail(SEMTSDF_ERR_INVALID, "NULL outputs: no frame map requested");
+    if (v->p.z_nshards != 1) return fail(SEMTSDF_ERR_UNSUPPORTED, "frame maps on a Z-sharded handle are not supported");
+    return SEMTSDF_OK;
+}
+
+static int frame_maps_impl(semtsdf_vol* v, const uint16_t* depth_d, float* vertex_d, float* normal_d,
+                           uint8_t* flags_d, hipStream_t s) {
+    FrameMapsArgs a{};
+    a.depth = depth_d;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) a.Kinv[i * 3 + j] = v->p.Kinv[i * 4 + j];
+    a.depth_scale = v->p.depth_scale;
+    a.width = v->p.width;
+    a.height = v->p.height;
+    a.vertex = vertex_d;
+    a.normal = normal_d;
+    a.flags = flags_d;
+    HIPC(launch_frame_maps(a, s));
+    return SEMTSDF_OK;
+}
+
+int semtsdf_frame_maps_dev(semtsdf_vol* v, const uint16_t* depth_d, float* vertex_d, float* normal_d,
+                           uint8_t* flags_d, void* stream) {
+    if (int rc = frame_maps_check(v, depth_d, vertex_d, normal_d, flags_d)) return rc;
+    HIPC(hipSetDevice(v->device));
+    return frame_maps_impl(v, depth_d, vertex_d, normal_d, flags_d, pick(v, stream));
+}
+
+int semtsdf_frame_maps(semtsdf_vol* v, const uint16_t* depth, float* vertex, float* normal, uint8_t* flags,
+                       void* stream) {
+    if (int rc = frame_maps_check(v, depth, vertex, normal, flags)) return rc;
+    HIPC(hipSetDevice(v->device));
+    hipStream_t s = pick(v, stream);
+    const size_t n = npx(v);
+    if (int rc = track_scratch(v)) return rc;
+    float* f = reinterpret_cast<float*>(v->track_d);
+    float* vertex_d = vertex ? f : nullptr;
+    float* normal_d = normal ? f + n * 3 : nullptr;
+    uint8_t* flags_d = flags ? v->track_d + n * 48 + kIcpWords * 8 : nullptr;
+    uint16_t* depth_d = reinterpret_cast<uint16_t*>(v->track_d + n * 50 + kIcpWords * 8);
+    HIPC(hipMemcpyAsync(depth_d, depth, n * 2, hipMemcpyHostToDevice, s));
+    if (int rc = frame_maps_impl(v, depth_d, vertex_d, normal_d, flags_d, s)) return rc;
+    if (vertex) HIPC(hipMemcpyAsync(vertex, vertex_d, n * 12, hipMemcpyDeviceToHost, s));
+    if (normal) HIPC(hipMemcpyAsync(normal, normal_d, n * 12, hipMemcpyDeviceToHost, s));
+    if (flags) HIPC(hipMemcpyAsync(flags, flags_d, n, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    return SEMTSDF_OK;
+}
+
+// Argument checks of the system, all before any device work.
+static int icp_check(semtsdf_vol* v, const semtsdf_icp_in* in, const float* E_ref, const float* E_cur, float dist_max,
+                     float cos_min, int32_t stride, const int64_t* words) {
+    if (!v || !in || !E_ref || !E_cur || !words) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
+    if (!in->vertex || !in->normal || !in->flags || !in->m_point || !in->m_normal || !in->m_flags)
+        return fail(SEMTSDF_ERR_INVALID, "NULL input map");
+    if (npx(v) > ((size_t)1 << 19))
+        return fail(SEMTSDF_ERR_INVALID, "image %d x %d has more than 2^19 pixels (the bound of the integer sums)",
+                    v->p.width, v->p.height);
+    if (stride < 1) return fail(SEMTSDF_ERR_INVALID, "stride=%d must be >= 1", (int)stride);
+    if (!(dist_max > 0.0f && dist_max <= 1.0f))
+        return fail(SEMTSDF_ERR_INVALID, "dist_max=%g outside (0, 1]", (double)dist_max);
+    if (!(cos_min >= -1.0f && cos_min <= 1.0f))
+        return fail(SEMTSDF_ERR_INVALID, "cos_min=%g outside [-1, 1]", (double)cos_min);
+    if (v->p.z_nshards != 1)
+        return fail(SEMTSDF_ERR_UNSUPPORTED, "the ICP system on a Z-sharded handle is not supported");
+    return SEMTSDF_OK;
+}
+
+static int icp_impl(semtsdf_vol* v, const semtsdf_icp_in& in_d, const float E_ref[16], const float E_cur[16],
+                    float dist_max, float cos_min, int32_t stride, int64_t* words_d, hipStream_t s) {
+    IcpArgs a{};
+    a.vertex = in_d.vertex; a.normal = in_d.normal; a.flags = in_d.flags;
+    a.m_point = in_d.m_point; a.m_normal = in_d.m_normal; a.m_flags = in_d.m_flags;
+    for (int i = 0; i < 3; ++i) {  // Rt, o of E_cur: semtsdf_pose_camera's sums of double products, rounded once
+        double acc = 0;
+        for (int k = 0; k < 3; ++k) acc += (double)E_cur[k * 4 + i] * (double)E_cur[k * 4 + 3];
+        a.o[i] = (float)(-acc);
+        for (int j = 0; j < 3; ++j) {
+            a.Rt[i * 3 + j] = E_cur[j * 4 + i];
+            a.K[i * 3 + j] = v->p.K[i * 4 + j];
+        }
+    }
+    fill_E(a.Eref, E_ref);
+    a.dmax2 = dist_max * dist_max;
+    a.cos_min = cos_min;
+    a.stride = stride;
+    a.width = v->p.width;
+    a.height = v->p.height;
+    a.words = reinterpret_cast<long long*>(words_d);
+    HIPC(hipMemsetAsync(words_d, 0, kIcpWords * 8, s));
+    HIPC(launch_icp_system(a, s));
+    return SEMTSDF_OK;
+}
+
+int semtsdf_icp_system_dev(semtsdf_vol* v, const semtsdf_icp_in* in_dev, const float E_ref[16],
+                           const float E_cur[16], float dist_max, float cos_min, int32_t stride, int64_t* words_dev,
+                           void* stream) {
+    if (int rc = icp_check(v, in_dev, E_ref, E_cur, dist_max, cos_min, stride, words_dev)) return rc;
+    HIPC(hipSetDevice(v->device));
+    return icp_impl(v, *in_dev, E_ref, E_cur, dist_max, cos_min, stride, words_dev, pick(v, stream));
+}
+
+int semtsdf_icp_system(semtsdf_vol* v, const semtsdf_icp_in* in_host, const float E_ref[16], const float E_cur[16],
+                       float dist_max, float cos_min, int32_t stride, int64_t* words_host, void* stream) {
+    if (int rc = icp_check(v, in_host, E_ref, E_cur, dist_max, cos_min, stride, words_host)) return rc;
+    HIPC(hipSetDevice(v->device));
+    hipStream_t s = pick(v, stream);
+    const size_t n = npx(v);
+    if (int rc = track_scratch(v)) return rc;
+    float* f = reinterpret_cast<float*>(v->track_d);
+    uint8_t* b = v->track_d + n * 48 + kIcpWords * 8;
+    int64_t* words_d = reinterpret_cast<int64_t*>(v->track_d + n * 48);
+    HIPC(hipMemcpyAsync(f, in_host->vertex, n * 12, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(f + n * 3, in_host->normal, n * 12, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(f + n * 6, in_host->m_point, n * 12, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(f + n * 9, in_host->m_normal, n * 12, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(b, in_host->flags, n, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(b + n, in_host->m_flags, n, hipMemcpyHostToDevice, s));
+    semtsdf_icp_in d{f, f + n * 3, b, f + n * 6, f + n * 9, b + n};
+    if (int rc = icp_impl(v, d, E_ref, E_cur, dist_max, cos_min, stride, words_d, s)) return rc;
+    HIPC(hipMemcpyAsync(words_host, words_d, kIcpWords * 8, hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
     return SEMTSDF_OK;
 }

@@ -291,6 +291,36 @@ struct MapsArgs {
     uint8_t* flags;    // [npx]
 };
 
+// Frame maps of a depth image (k_frame_maps): camera-space vertex, normal, validity byte, each nullable.
+struct FrameMapsArgs {
+    const uint16_t* depth;  // [npx]
+    float Kinv[9];
+    float depth_scale;
+    int width, height;
+    float* vertex;          // [npx][3]
+    float* normal;          // [npx][3]
+    uint8_t* flags;         // [npx]
+};
+
+constexpr int kIcpWords = 32;  // SEMTSDF_ICP_WORDS
+
+// The point-to-plane system of one ICP iteration (k_icp_system, include/semtsdf.h).
+struct IcpArgs {
+    const float* vertex;    // frame maps
+    const float* normal;
+    const uint8_t* flags;
+    const float* m_point;   // model maps of the reference view
+    const float* m_normal;
+    const uint8_t* m_flags;
+    float Rt[9], o[3];      // of E_cur (pose_camera's rule)
+    float Eref[12];
+    float K[9];
+    float dmax2, cos_min;
+    int stride;
+    int width, height;
+    long long* words;       // [kIcpWords], zeroed before the launch
+};
+
 // Z-sharded raycast protocol (k_shard_* in semtsdf_kernels.hip): per-pixel march state.
 struct ShardRayState {
     int* k;      // global coarse event index, -1 = miss
@@ -374,6 +404,8 @@ hipError_t launch_first_frame_objs(const AssocTables* t, int* num_objs_dev, hipS
 hipError_t launch_relabel(uint8_t* mask, int npx, const AssocDecision* d, hipStream_t s);
 hipError_t launch_render(const RenderArgs& a, hipStream_t s);
 hipError_t launch_model_maps(const MapsArgs& a, hipStream_t s);
+hipError_t launch_frame_maps(const FrameMapsArgs& a, hipStream_t s);
+hipError_t launch_icp_system(const IcpArgs& a, hipStream_t s);
 hipError_t launch_march_fused(const AssocArgs& aa, const RenderArgs& ra, hipStream_t s);
 hipError_t launch_copy_host(const void* src, void* dst, size_t n16, hipStream_t s);
 // chunk [v0, v0+nv) of the bin-major histogram <-> voxel-major [nv][32] staging buffer

@@ -3559,6 +3559,191 @@ hipError_t launch_model_maps(const MapsArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------
+// camera tracking (include/semtsdf.h, "camera tracking"): the frame maps of a depth image and
+// the point-to-plane system of one ICP iteration.  Two flat per-pixel kernels, no march; the
+// volume is not read.  No reference counterpart.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ void cross3(const float a[3], const float b[3], float out[3]) {
+    out[0] = a[1] * b[2] - a[2] * b[1];
+    out[1] = a[2] * b[0] - a[0] * b[2];
+    out[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// V = (Kinv (x, y, 1)) * (d / depth_scale) of a pixel with nonzero raw depth d
+__device__ __forceinline__ void frame_vertex(const FrameMapsArgs& a, int x, int y, unsigned d, float V[3]) {
+    const float z = (float)d / a.depth_scale;
+    const float fx = (float)x, fy = (float)y;
+    V[0] = dot3(a.Kinv[0], a.Kinv[1], a.Kinv[2], fx, fy, 1.0f) * z;
+    V[1] = dot3(a.Kinv[3], a.Kinv[4], a.Kinv[5], fx, fy, 1.0f) * z;
+    V[2] = dot3(a.Kinv[6], a.Kinv[7], a.Kinv[8], fx, fy, 1.0f) * z;
+}
+
+__global__ __launch_bounds__(256) void k_frame_maps(FrameMapsArgs a) {
+    const int x = (int)blockIdx.x * 16 + (int)(threadIdx.x & 15);
+    const int y = (int)blockIdx.y * 16 + (int)(threadIdx.x >> 4);
+    if (x >= a.width || y >= a.height) return;
+    const size_t px = (size_t)y * a.width + x;
+    const unsigned d = a.depth[px];
+    float V[3] = {0.0f, 0.0f, 0.0f}, n[3] = {0.0f, 0.0f, 0.0f};
+    unsigned fl = 0;
+    if (d) {
+        fl = 1u;
+        frame_vertex(a, x, y, d, V);
+        if ((a.normal || a.flags) && x + 1 < a.width && y + 1 < a.height) {
+            const unsigned dr = a.depth[px + 1], dd = a.depth[px + (size_t)a.width];
+            if (dr && dd) {
+                float A[3], B[3], g[3];
+                frame_vertex(a, x, y + 1, dd, A);
+                frame_vertex(a, x + 1, y, dr, B);
+                for (int k = 0; k < 3; ++k) {
+                    A[k] -= V[k];
+                    B[k] -= V[k];
+                }
+                cross3(A, B, g);
+                const float n2 = dot3(g[0], g[1], g[2], g[0], g[1], g[2]);
+                if (n2 > 0.0f && n2 < __builtin_inff()) {
+                    const float inv = 1.0f / sqrtf(n2);
+                    n[0] = g[0] * inv;
+                    n[1] = g[1] * inv;
+                    n[2] = g[2] * inv;
+                    fl |= 2u;
+                }
+            }
+        }
+    }
+    if (a.vertex) {
+        a.vertex[px * 3 + 0] = V[0];
+        a.vertex[px * 3 + 1] = V[1];
+        a.vertex[px * 3 + 2] = V[2];
+    }
+    if (a.normal) {
+        a.normal[px * 3 + 0] = n[0];
+        a.normal[px * 3 + 1] = n[1];
+        a.normal[px * 3 + 2] = n[2];
+    }
+    if (a.flags) a.flags[px] = (uint8_t)fl;
+}
+
+hipError_t launch_frame_maps(const FrameMapsArgs& a, hipStream_t s) {
+    const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
+    hipLaunchKernelGGL(k_frame_maps, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// RN(a * b * 2^32) as an integer: the double product of two f32 values is exact, and so is the
+// scaling; |a b| < 2^10 by the range gate, so the result is far inside int64.
+__device__ __forceinline__ long long icp_fix(float a, float b) {
+    return __double2ll_rn((double)a * (double)b * 4294967296.0);
+}
+
+constexpr int kIcpSums = 28;  // words 0..27: J^T J (21), J^T r (6), sum r^2; 28..31 are the class counts
+
+// One thread per visited pixel (16 x 16 tiles of the strided pixel grid).  An inlier's 28 terms are
+// summed over the wave by a butterfly of shuffles (both halves of each word), the four class
+// counts come from ballots; the waves of a workgroup meet in LDS and the workgroup adds each
+// nonzero word to the output with one 64-bit integer atomic.  Integer sums: no order dependence.
+__global__ __launch_bounds__(256) void k_icp_system(IcpArgs a) {
+    __shared__ long long red[4][kIcpWords];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long xl = ((long long)blockIdx.x * 16 + (tid & 15)) * a.stride;
+    const long long yl = ((long long)blockIdx.y * 16 + (tid >> 4)) * a.stride;
+    int cls = -1;  // 0 inlier, 1 far, 2 angle, 3 none; -1: not visited
+    float J[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, r = 0.0f;
+    if (xl < a.width && yl < a.height) {
+        const size_t px = (size_t)yl * a.width + (size_t)xl;
+        if ((a.flags[px] & 3u) == 3u) {
+            cls = 3;
+            const float V0 = a.vertex[px * 3 + 0], V1 = a.vertex[px * 3 + 1], V2 = a.vertex[px * 3 + 2];
+            float Pw[3];
+            Pw[0] = dot3(a.Rt[0], a.Rt[1], a.Rt[2], V0, V1, V2) + a.o[0];
+            Pw[1] = dot3(a.Rt[3], a.Rt[4], a.Rt[5], V0, V1, V2) + a.o[1];
+            Pw[2] = dot3(a.Rt[6], a.Rt[7], a.Rt[8], V0, V1, V2) + a.o[2];
+            const float qx = dot3(a.Eref[0], a.Eref[1], a.Eref[2], Pw[0], Pw[1], Pw[2]) + a.Eref[3];
+            const float qy = dot3(a.Eref[4], a.Eref[5], a.Eref[6], Pw[0], Pw[1], Pw[2]) + a.Eref[7];
+            const float qz = dot3(a.Eref[8], a.Eref[9], a.Eref[10], Pw[0], Pw[1], Pw[2]) + a.Eref[11];
+            const float sx = dot3(a.K[0], a.K[1], a.K[2], qx, qy, qz);
+            const float sy = dot3(a.K[3], a.K[4], a.K[5], qx, qy, qz);
+            const float sz = dot3(a.K[6], a.K[7], a.K[8], qx, qy, qz);
+            const float u = floorf(sx / sz + 0.5f), v = floorf(sy / sz + 0.5f);
+            if (!(qz <= 0.0f) && u >= 0.0f && u < (float)a.width && v >= 0.0f && v < (float)a.height) {
+                const size_t mp = (size_t)(int)v * a.width + (size_t)(int)u;
+                if ((a.m_flags[mp] & 3u) == 3u) {
+                    float Nm[3], d[3];
+                    for (int k = 0; k < 3; ++k) {
+                        Nm[k] = a.m_normal[mp * 3 + k];
+                        d[k] = a.m_point[mp * 3 + k] - Pw[k];
+                    }
+                    if (dot3(d[0], d[1], d[2], d[0], d[1], d[2]) > a.dmax2) {
+                        cls = 1;
+                    } else {
+                        const float n0 = a.normal[px * 3 + 0], n1 = a.normal[px * 3 + 1], n2 = a.normal[px * 3 + 2];
+                        const float w0 = dot3(a.Rt[0], a.Rt[1], a.Rt[2], n0, n1, n2);
+                        const float w1 = dot3(a.Rt[3], a.Rt[4], a.Rt[5], n0, n1, n2);
+                        const float w2 = dot3(a.Rt[6], a.Rt[7], a.Rt[8], n0, n1, n2);
+                        if (dot3(Nm[0], Nm[1], Nm[2], w0, w1, w2) < a.cos_min) {
+                            cls = 2;
+                        } else {
+                            r = dot3(Nm[0], Nm[1], Nm[2], d[0], d[1], d[2]);
+                            cross3(Pw, Nm, J);
+                            J[3] = Nm[0];
+                            J[4] = Nm[1];
+                            J[5] = Nm[2];
+                            bool in = true;
+                            for (int k = 0; k < 6; ++k) in = in && fabsf(J[k]) < 32.0f;
+                            if (in) cls = 0;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    // the ballots are taken by the whole wave, before lane 0 alone stores their counts
+    const unsigned long long inl = __ballot(cls == 0), far = __ballot(cls == 1), ang = __ballot(cls == 2),
+                             non = __ballot(cls == 3);
+    if (lane == 0) {
+        red[wave][28] = (long long)__popcll(inl);
+        red[wave][29] = (long long)__popcll(far);
+        red[wave][30] = (long long)__popcll(ang);
+        red[wave][31] = (long long)__popcll(non);
+    }
+    if (inl) {  // wave-uniform
+        long long acc[kIcpSums];
+        if (cls != 0) {
+            for (int k = 0; k < 6; ++k) J[k] = 0.0f;
+            r = 0.0f;
+        }
+        int w = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) acc[w++] = icp_fix(J[i], J[j]);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) acc[21 + i] = icp_fix(J[i], r);
+        acc[27] = icp_fix(r, r);
+#pragma unroll
+        for (int k = 0; k < kIcpSums; ++k) {
+            long long s = acc[k];
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+            if (lane == 0) red[wave][k] = s;
+        }
+    } else if (lane < kIcpSums) {
+        red[wave][lane] = 0;
+    }
+    __syncthreads();
+    if (tid < kIcpWords) {
+        const long long s = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+        if (s) atomicAdd(reinterpret_cast<unsigned long long*>(a.words) + tid, (unsigned long long)s);
+    }
+}
+
+hipError_t launch_icp_system(const IcpArgs& a, hipStream_t s) {
+    const int nx = (a.width - 1) / a.stride + 1, ny = (a.height - 1) / a.stride + 1;  // visited pixels
+    const dim3 grid((nx + 15) / 16, (ny + 15) / 16);
+    hipLaunchKernelGGL(k_icp_system, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
 // Z-sharded raycast.  The march of march_ray is sequential along the ray
 // (sticky quarter step, refinement from the previous sample), so it is split into steps
 // that every rank of the group runs on its own planes, with an all-gather of one 8-byte

@@ -11,8 +11,9 @@ from .config import Configuration, FusionConfig
 from .export import (export_surface, extract_mesh, merge_meshes, read_mesh_ply, read_ply, write_mesh_ply,
                      write_ply)
 from .instances import find_duplicates, instance_stats, merge_instance_stats, plan_remap
-from . import maps
+from . import maps, track
 from .maps import pose_camera, shade_normals, z_depth
+from .track import TrackingLost
 from .tsdf import TSDF
 from .volume import DeviceBuffer, Volume, default_params, orbit_camera, place_from_frame
 
@@ -20,5 +21,5 @@ __all__ = ["TSDF", "Volume", "DeviceBuffer", "Configuration", "FusionConfig", "S
            "default_params", "place_from_frame", "orbit_camera", "_lib", "export_surface", "write_ply", "read_ply",
            "extract_mesh", "merge_meshes", "write_mesh_ply", "read_mesh_ply",
            "instance_stats", "merge_instance_stats", "find_duplicates", "plan_remap",
-           "maps", "pose_camera", "z_depth", "shade_normals",
+           "maps", "pose_camera", "z_depth", "shade_normals", "track", "TrackingLost",
            "RENDER_LABEL", "RENDER_COLOR", "RAY_ASSOC", "PLACE_SFM", "PLACE_PYTHON"]

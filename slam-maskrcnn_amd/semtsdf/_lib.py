@@ -122,6 +122,13 @@ class MapsOut(C.Structure):
                 ("votes", C.c_void_p), ("flags", C.c_void_p)]
 
 
+class IcpIn(C.Structure):
+    """semtsdf_icp_in: the frame maps and the model maps of the reference view."""
+    _fields_ = [("vertex", C.c_void_p), ("normal", C.c_void_p), ("flags", C.c_void_p), ("m_point", C.c_void_p),
+                ("m_normal", C.c_void_p), ("m_flags", C.c_void_p)]
+
+
+ICP_WORDS = 32
 MAP_HIT = 0x1
 MAP_NORMAL = 0x2
 MAP_NAMES = ("t", "point", "normal", "label", "votes", "flags")
@@ -197,6 +204,10 @@ SIGNATURES = {
     "semtsdf_render_maps": (_I, [_P, _P, _P, C.c_int32, C.POINTER(MapsOut), _P]),
     "semtsdf_render_maps_dev": (_I, [_P, _P, _P, C.c_int32, C.POINTER(MapsOut), _P]),
     "semtsdf_pose_camera": (_I, [_P, _P, _P, _P]),
+    "semtsdf_frame_maps": (_I, [_P, _P, _P, _P, _P, _P]),
+    "semtsdf_frame_maps_dev": (_I, [_P, _P, _P, _P, _P, _P]),
+    "semtsdf_icp_system": (_I, [_P, C.POINTER(IcpIn), _P, _P, _F, _F, C.c_int32, _P, _P]),
+    "semtsdf_icp_system_dev": (_I, [_P, C.POINTER(IcpIn), _P, _P, _F, _F, C.c_int32, _P, _P]),
     "semtsdf_shard_ray_begin": (_I, [_P, _I, _P, _P, _I, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "semtsdf_shard_ray_step": (_I, [_P, _I, _P, _P, _P]),
     "semtsdf_shard_render_finish": (_I, [_P, _P, _P, _P, _P]),

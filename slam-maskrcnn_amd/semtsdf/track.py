@@ -1,0 +1,182 @@
+"""Camera tracking against the fused model: frame-to-model point-to-plane ICP.
+
+The device does the per-pixel work (include/semtsdf.h, "camera tracking"): the model maps of a
+reference view (semtsdf_render_maps_dev), the frame maps of the depth image
+(semtsdf_frame_maps_dev) and, per iteration, the normal equations as 32 fixed-point int64 words
+(semtsdf_icp_system_dev).  This module is the host side, NumPy float64 like pose.py: it scales the
+words back, solves the 6 x 6 system and moves the pose.
+
+Conventions.  E is the integrate's extrinsic: volume frame to camera, so C2W = E^-1 is the camera's
+pose in the volume frame.  A step is a twist xi = (omega, v) of the volume frame:
+C2W <- exp(xi) C2W.  The residual of a pixel is r = Nm . (Pm - Pw) and its row J = (Pw x Nm, Nm), so
+r - J xi is the residual after the step to first order, and xi solves (J^T J) xi = J^T r.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _lib as L
+
+SCALE = 2.0 ** -32          # one unit of the fixed-point sums
+SMALL_ANGLE = 1e-2          # |omega| below which exp() uses its series
+STEP_EPS = 1e-5             # |xi| (radians and metres together) below which the loop stops
+COUNT_NAMES = ("inliers", "far", "angle", "none")
+
+
+class TrackingLost(RuntimeError):
+    """Too few inliers to trust a step.  `E` is the estimate the loop had reached (f32 extrinsic),
+    `log` its per-iteration log up to and including the failing iteration."""
+
+    def __init__(self, msg, E, log):
+        super().__init__(msg)
+        self.E = E
+        self.log = log
+
+
+def system_from_words(words):
+    """(A, b, r2, counts) of the 32 int64 words: the symmetric 6 x 6 A = J^T J, b = J^T r and
+    r2 = sum r^2 scaled back by 2^-32 (float64), and the four class counts as a dict of ints."""
+    w = np.asarray(words, np.int64).reshape(L.ICP_WORDS)
+    A = np.zeros((6, 6), np.float64)
+    iu = np.triu_indices(6)  # row-major upper triangle: the word order
+    A[iu] = w[:21].astype(np.float64) * SCALE
+    A = A + np.triu(A, 1).T
+    b = w[21:27].astype(np.float64) * SCALE
+    counts = {n: int(w[28 + k]) for k, n in enumerate(COUNT_NAMES)}
+    return A, b, float(w[27]) * SCALE, counts
+
+
+def solve_step(A, b):
+    """xi of A xi = b (np.linalg.solve); raises numpy.linalg.LinAlgError on a singular or
+    non-finite system."""
+    A = np.asarray(A, np.float64)
+    b = np.asarray(b, np.float64)
+    if not (np.isfinite(A).all() and np.isfinite(b).all()):
+        raise np.linalg.LinAlgError("non-finite system")
+    return np.linalg.solve(A, b)
+
+
+def se3_exp(xi):
+    """The 4 x 4 rigid motion exp(xi) of a twist xi = (omega, v), float64: R = I + a K + b K^2 (Rodrigues)
+    and t = (I + b K + c K^2) v with K = [omega]x, th = |omega|, a = sin th / th,
+    b = (1 - cos th) / th^2 = 2 sin^2(th / 2) / th^2, c = (th - sin th) / th^3.  Below th = SMALL_ANGLE
+    the series a = 1 - th^2/6 + th^4/120, b = 1/2 - th^2/24 + th^4/720, c = 1/6 - th^2/120 + th^4/5040,
+    whose truncation error is below 2e-16 there; above it the cancellation in th - sin th costs c at most
+    6 eps / th^2 < 2e-11 of its value, which reaches t only through K^2 (th^2)."""
+    xi = np.asarray(xi, np.float64).reshape(6)
+    w, v = xi[:3], xi[3:]
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    K2 = K @ K
+    th = math.sqrt(float(w @ w))
+    t2 = th * th
+    if th < SMALL_ANGLE:
+        a = 1.0 - t2 / 6.0 + t2 * t2 / 120.0
+        b = 0.5 - t2 / 24.0 + t2 * t2 / 720.0
+        c = 1.0 / 6.0 - t2 / 120.0 + t2 * t2 / 5040.0
+    else:
+        h = math.sin(0.5 * th)
+        a, b, c = math.sin(th) / th, 2.0 * h * h / t2, (th - math.sin(th)) / (t2 * th)
+    T = np.eye(4)
+    T[:3, :3] = np.eye(3) + a * K + b * K2
+    T[:3, 3] = (np.eye(3) + b * K + c * K2) @ v
+    return T
+
+
+def se3_apply(xi, E):
+    """The extrinsic after the step xi: C2W_new = exp(xi) C2W with C2W = E^-1, inverted again and
+    rounded once to float32."""
+    c2w = np.linalg.inv(np.asarray(E, np.float64).reshape(4, 4))
+    return np.linalg.inv(se3_exp(xi) @ c2w).astype(np.float32)
+
+
+def default_min_inliers(width, height, stride):
+    """1 % of the pixels a stride visits at most (at least 6: the unknowns)."""
+    return max(6, (((width - 1) // stride + 1) * ((height - 1) // stride + 1)) // 100)
+
+
+def track_loop(system, E0, iters=10, min_inliers=6, eps=STEP_EPS):
+    """The ICP loop over any source of the words: system(E_cur) -> 32 int64 words.  Returns
+    (E, log): the f32 extrinsic after at most `iters` steps (fewer when a step's |xi| falls below
+    eps) and one dict per iteration with the four counts, rms = sqrt(sum r^2 / inliers) before the
+    step and step = |xi|.  Raises TrackingLost (estimate and log kept) when an iteration finds
+    fewer than min_inliers inliers, or its system cannot be solved."""
+    E = np.asarray(E0, np.float32).reshape(4, 4).copy()
+    log = []
+    for it in range(int(iters)):
+        A, b, r2, counts = system_from_words(system(E))
+        n = counts["inliers"]
+        entry = dict(counts, iter=it, rms=math.sqrt(r2 / n) if n else float("nan"), step=float("nan"))
+        log.append(entry)
+        if n < min_inliers:
+            raise TrackingLost(f"iteration {it}: {n} inliers, fewer than {min_inliers}", E, log)
+        try:
+            xi = solve_step(A, b)
+        except np.linalg.LinAlgError as e:
+            raise TrackingLost(f"iteration {it}: {e}", E, log) from e
+        entry["step"] = float(np.linalg.norm(xi))
+        E = se3_apply(xi, E)
+        if entry["step"] < eps:
+            break
+    return E, log
+
+
+def track(vol, depth, E_ref, E0, iters=10, dist_max=0.1, cos_min=0.8, stride=1, min_weight=1, min_inliers=None,
+          eps=STEP_EPS):
+    """Tracks the depth image (u16 [H, W]) against the model in `vol`, starting from the extrinsic
+    E0.  The model maps are rendered once at pose_camera(Kinv, E_ref) (min_weight: the maps'
+    validity threshold) and stay on the device, as do the frame maps; each iteration is one
+    launch and a 256-byte read-back.  min_inliers defaults to default_min_inliers.  Returns
+    (E, log) as track_loop does, and raises TrackingLost like it."""
+    from .maps import pose_camera
+    from .volume import DeviceBuffer
+
+    d = np.ascontiguousarray(depth, dtype=np.uint16)
+    n = vol.W * vol.H
+    if d.size != n:
+        raise ValueError(f"depth must be {vol.H}x{vol.W} u16")
+    if min_inliers is None:
+        min_inliers = default_min_inliers(vol.W, vol.H, int(stride))
+    E_ref = L.f32(E_ref, 16)
+    s2w, c = pose_camera(list(vol.params.Kinv), E_ref)
+    stream = C.c_void_p(vol.stream)
+    sizes = {"depth": 2 * n, "vertex": 12 * n, "normal": 12 * n, "flags": n, "m_point": 12 * n, "m_normal": 12 * n,
+             "m_flags": n, "words": 8 * L.ICP_WORDS}
+    bufs = {}
+    try:
+        for k, size in sizes.items():
+            bufs[k] = DeviceBuffer(size)
+        vol.render_maps_dev(s2w, c, int(min_weight), point=bufs["m_point"].ptr, normal=bufs["m_normal"].ptr,
+                            flags=bufs["m_flags"].ptr)
+        bufs["depth"].upload(d, stream)
+        vol.frame_maps_dev(bufs["depth"].ptr, bufs["vertex"].ptr, bufs["normal"].ptr, bufs["flags"].ptr)
+        pointers = [bufs[k].ptr for k in ("vertex", "normal", "flags", "m_point", "m_normal", "m_flags")]
+        words = np.zeros(L.ICP_WORDS, np.int64)
+
+        def system(E):
+            vol.icp_system_dev(pointers, E_ref, E, dist_max, cos_min, stride, bufs["words"].ptr)
+            bufs["words"].download(words, stream)
+            vol.sync()
+            return words
+
+        return track_loop(system, E0, iters, min_inliers, eps)
+    finally:
+        vol.sync()
+        for b in bufs.values():
+            b.free()
+
+
+def pose_errors(E, E_true):
+    """(translation error in metres, rotation angle in radians) between two extrinsics, measured
+    on the camera poses C2W = E^-1."""
+    a = np.linalg.inv(np.asarray(E, np.float64).reshape(4, 4))
+    b = np.linalg.inv(np.asarray(E_true, np.float64).reshape(4, 4))
+    dR = a[:3, :3].T @ b[:3, :3]
+    ang = math.acos(max(-1.0, min(1.0, (np.trace(dR) - 1.0) / 2.0)))
+    return float(np.linalg.norm(a[:3, 3] - b[:3, 3])), ang
+
+
+__all__ = ["TrackingLost", "system_from_words", "solve_step", "se3_exp", "se3_apply", "track_loop", "track",
+           "pose_errors", "default_min_inliers", "STEP_EPS"]

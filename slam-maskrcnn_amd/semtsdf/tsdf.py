@@ -59,6 +59,8 @@ class TSDF:
         self.N = 0
         self.vol: Volume | None = None
         self.last_assoc: L.AssocStats | None = None
+        self.last_extrinsic = None   # W2C of the last fused frame: TSDF.track's default guess
+        self.last_track = None       # per-iteration log of the last TSDF.track
 
     # ------------------------------------------------------------------ placement (a1)
     def _flags(self) -> int:
@@ -152,6 +154,7 @@ class TSDF:
             masks[...] = m  # relabelled in place (tsdf.cu:376-386: Mat& masks)
         self.N += 1
         self.last_assoc = st
+        self.last_extrinsic = np.array(extrinsic, dtype=np.float64)
         return st
 
     def _vote_frame(self, depth, color, cls, E):
@@ -261,6 +264,23 @@ class TSDF:
         sem = bool(self.vol.params.flags & L.F_SEMANTIC)
         want = tuple(n for n in L.MAP_NAMES if sem or n not in ("label", "votes"))
         return self.vol.render_maps(s2w, c, min_weight, want)
+
+    # ------------------------------------------------------------------ tracking
+    def track(self, depth, guess=None, **kw):
+        """The W2C extrinsic of a depth image, tracked against the fused model by point-to-plane ICP
+        (semtsdf.track.track; **kw are its options): the pose to hand to parse_frame for this frame.
+        `guess` is a W2C extrinsic as parse_frame takes it, by default the last fused frame's; the
+        model is viewed from it.  Raises semtsdf.track.TrackingLost when too few pixels match.  The
+        per-iteration log is kept in `last_track`."""
+        from .track import track
+
+        if guess is None:
+            guess = self.last_extrinsic
+        if guess is None or self.vol is None:
+            raise ValueError("nothing fused yet: no model to track against")
+        E0 = P.relative_pose(guess, self.init_extrinsic_inv)
+        E, self.last_track = track(self.vol, depth, E0, E0, **kw)
+        return E.astype(np.float64) @ np.linalg.inv(np.asarray(self.init_extrinsic_inv, np.float64))
 
     def orbit(self, n: int, out_dir: str | None = None, mode: str = "label", step: float = 0.01, callback=None):
         """The reference's view loop (kernel.cpp:101-107: angle += 0.01 per view at the mean

@@ -266,6 +266,59 @@ class Volume:
         cc = L.f32(c, 3)
         L.check(L.load().semtsdf_render_maps_dev(self._h, L.ptr(s), L.ptr(cc), int(min_weight), C.byref(o), stream))
 
+    # ---- camera tracking (semtsdf/track.py drives these)
+    def frame_maps(self, depth, want=("vertex", "normal", "flags")) -> dict:
+        """The frame maps of a depth image (semtsdf_frame_maps): camera-space vertex and normal f32
+        [H, W, 3] and the validity byte u8 [H, W] (bit 0: depth, bit 1: normal) named in `want`."""
+        d = np.ascontiguousarray(depth, dtype=np.uint16)
+        if d.size != self.W * self.H:
+            raise ValueError(f"depth must be {self.H}x{self.W} u16")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        shapes = {"vertex": ((self.H, self.W, 3), np.float32), "normal": ((self.H, self.W, 3), np.float32),
+                  "flags": ((self.H, self.W), np.uint8)}
+        bad = [w for w in want if w not in shapes]
+        if bad:
+            raise ValueError(f"unknown frame map {bad[0]!r} (one of {', '.join(shapes)})")
+        out = {k: np.zeros(*shapes[k]) for k in want}
+        L.check(L.load().semtsdf_frame_maps(self._h, L.ptr(d), L.ptr(out.get("vertex")), L.ptr(out.get("normal")),
+                                            L.ptr(out.get("flags")), None))
+        return out
+
+    def frame_maps_dev(self, depth_ptr: int, vertex: int | None = None, normal: int | None = None,
+                       flags: int | None = None, stream=None):
+        """frame_maps from and into device buffers (raw pointers), asynchronous on `stream`."""
+        L.check(L.load().semtsdf_frame_maps_dev(self._h, C.c_void_p(depth_ptr), *[C.c_void_p(p) if p else None
+                                                                                    for p in (vertex, normal, flags)],
+                                                stream))
+
+    def icp_system(self, frame: dict, model: dict, E_ref, E_cur, dist_max: float = 0.1, cos_min: float = 0.8,
+                   stride: int = 1) -> np.ndarray:
+        """The 32 int64 words of one ICP iteration's point-to-plane system (semtsdf_icp_system) from
+        host arrays: `frame` as frame_maps returns it, `model` the point, normal, flags of
+        render_maps at pose_camera(Kinv, E_ref)."""
+        n = self.W * self.H
+        arrs = [np.ascontiguousarray(frame["vertex"], np.float32), np.ascontiguousarray(frame["normal"], np.float32),
+                np.ascontiguousarray(frame["flags"], np.uint8), np.ascontiguousarray(model["point"], np.float32),
+                np.ascontiguousarray(model["normal"], np.float32), np.ascontiguousarray(model["flags"], np.uint8)]
+        for a, ch in zip(arrs, (3, 3, 1, 3, 3, 1)):
+            if a.size != n * ch:
+                raise ValueError(f"maps must be {self.H}x{self.W}")
+        words = np.zeros(L.ICP_WORDS, np.int64)
+        er, ec = L.f32(E_ref, 16), L.f32(E_cur, 16)
+        L.check(L.load().semtsdf_icp_system(self._h, C.byref(L.IcpIn(*[a.ctypes.data for a in arrs])), L.ptr(er),
+                                            L.ptr(ec), float(dist_max), float(cos_min), int(stride), L.ptr(words),
+                                            None))
+        return words
+
+    def icp_system_dev(self, pointers, E_ref, E_cur, dist_max, cos_min, stride, words_ptr: int, stream=None):
+        """icp_system on device buffers: `pointers` the six raw pointers in semtsdf_icp_in order
+        (frame vertex, normal, flags; model point, normal, flags), `words_ptr` 32 int64 on the
+        device; asynchronous on `stream`, nothing is read back."""
+        er, ec = L.f32(E_ref, 16), L.f32(E_cur, 16)
+        L.check(L.load().semtsdf_icp_system_dev(self._h, C.byref(L.IcpIn(*[int(p) if p else None for p in pointers])),
+                                                L.ptr(er), L.ptr(ec), float(dist_max), float(cos_min), int(stride),
+                                                C.c_void_p(words_ptr) if words_ptr else None, stream))
+
     # ---- state transfer (reference layouts)
     def download(self, sdf=True, wt=True, color=True, hist=False, cls=False):
         n = self.nvox
