@@ -22,6 +22,7 @@
 
 #include "../../include/semtsdf.h"
 #include "semtsdf_internal.h"
+#include "semtsdf_wscan.h"
 
 using namespace semtsdf;
 
@@ -137,6 +138,11 @@ struct semtsdf_vol {
     bool color_wide = false;
     int64_t wmax_bound = 0;        // upper bound of every weight (uploads, +1 per integrate): byte storage
                                    // is left before a colour mean could take the int32 wrap (w >= 2^23)
+    // Weight storage: uint16_t while every weight lies in [0, 65535] -- a weight is at most the
+    // number of frames integrated -- and int32_t from the integrate that could pass 65535, or an
+    // upload with a value outside that range, onwards (one way, like color_wide; VolBufs::wt_wide is
+    // the kernels' copy).  The int32 boundary is unchanged.
+    bool wt_wide = false;
     const uint8_t* pending_lut = nullptr;  // relabel table the next integrate's prepass applies
     unsigned long long* wtrace_d = nullptr;  // instrumentation: per-wave trace slots (kWtSlots, allocated once)
     // launch order of the fused view + association march (AssocArgs::tile_*): per-tile durations
@@ -331,6 +337,20 @@ int widen_color(semtsdf_vol* v, hipStream_t s) {
     return SEMTSDF_OK;
 }
 
+// The weights leave uint16 storage for int32 (values converted on the device).
+int widen_weights(semtsdf_vol* v, hipStream_t s) {
+    if (v->wt_wide) return SEMTSDF_OK;
+    void* wide = nullptr;
+    if (int rc = dev_alloc(v, &wide, v->g.nvox * 4)) return rc;
+    HIPC(launch_weight_widen(static_cast<const uint16_t*>(v->b.wt), static_cast<int32_t*>(wide), v->g.nvox, s));
+    HIPC(hipStreamSynchronize(s));
+    HIPC(hipFree(v->b.wt));
+    v->device_bytes -= v->g.nvox * 2;
+    v->b.wt = wide;
+    v->wt_wide = true;
+    v->b.wt_wide = 1;
+    return SEMTSDF_OK;
+}
 
 int ensure_prep_stream(semtsdf_vol* v) {
     if (v->prep_stream) return SEMTSDF_OK;
@@ -363,6 +383,10 @@ int integrate_impl(semtsdf_vol* v, const uint16_t* depth_d, const uint8_t* rgb_d
     // before the kernel arguments are built, which copy the buffer pointers
     if ((v->p.flags & SEMTSDF_F_COLOR_I32) && !v->color_wide && v->wmax_bound + 1 >= (1ll << 23)) {
         if (int rc = widen_color(v, s)) return rc;
+    }
+    // uint16 weights hold every value up to 65535: this integrate could pass it
+    if (!v->wt_wide && v->wmax_bound + 1 > kNarrowWeightMax) {
+        if (int rc = widen_weights(v, s)) return rc;
     }
     IntegrateArgs a{};
     a.g = v->g;
@@ -952,7 +976,7 @@ int semtsdf_create(const semtsdf_params* p, int device, semtsdf_vol** out) {
         return bail(fail(SEMTSDF_ERR_HIP, "hipStreamCreate failed"));
     const bool ci32 = p->flags & SEMTSDF_F_COLOR_I32;
     if ((rc = dev_alloc(v, (void**)&v->b.sdf, n * 4))) return bail(rc);
-    if ((rc = dev_alloc(v, (void**)&v->b.wt, n * 4))) return bail(rc);
+    if ((rc = dev_alloc(v, &v->b.wt, n * 2))) return bail(rc);  // uint16 (wt_wide)
     if ((rc = dev_alloc(v, (void**)&v->b.sflag, n / 32 + 1))) return bail(rc);
     const size_t nbricks = (size_t)g.nbx * g.nby * g.nbz;
     if ((rc = dev_alloc(v, (void**)&v->b.bplain, nbricks * 4))) return bail(rc);
@@ -1082,7 +1106,17 @@ int semtsdf_reset(semtsdf_vol* v, void* stream) {
     const size_t n = v->g.nvox;
     if (int rc = after_maps(v, s)) return rc;
     HIPC(launch_fill_volume(v->g, v->b, v->p.flags, s));
-    HIPC(hipMemsetAsync(v->b.wt, 0, n * 4, s));
+    if (v->wt_wide) {  // all weights are 0 again: back to uint16 storage
+        void* narrow = nullptr;
+        if (int rc = dev_alloc(v, &narrow, n * 2)) return rc;
+        HIPC(hipStreamSynchronize(s));
+        HIPC(hipFree(v->b.wt));
+        v->device_bytes -= n * 4;
+        v->b.wt = narrow;
+        v->wt_wide = false;
+        v->b.wt_wide = 0;
+    }
+    HIPC(hipMemsetAsync(v->b.wt, 0, n * 2, s));
     HIPC(hipMemsetAsync(v->b.sflag, 0, n / 32 + 1, s));  // steady flags: unknown
     HIPC(hipMemsetAsync(v->b.color, 0, v->g.nvox * 4 * (v->color_wide ? 4 : 1), s));
     if (v->b.hist) HIPC(hipMemsetAsync(v->b.hist, 0, v->g.nvox * kMaxObjects * 4, s));
@@ -2050,8 +2084,9 @@ int semtsdf_icp_system(semtsdf_vol* v, const semtsdf_icp_in* in_host, const floa
 static uint64_t nref(const semtsdf_vol* v) { return (uint64_t)v->g.dimx * v->g.dimy * v->g.lz; }
 
 // Voxels [vb, ve) of the reference layout (host[0] is voxel vb).
+// dev_u16: the device array holds uint16_t (narrow weights), the host side int32 all the same.
 static int vox_xfer(semtsdf_vol* v, void* host, void* dev, bool to_host, const char* what, hipStream_t s, uint64_t vb,
-                    uint64_t ve) {
+                    uint64_t ve, bool dev_u16 = false) {
     if (ve <= vb) return SEMTSDF_OK;
     const uint64_t chunk = std::min<uint64_t>(ve - vb, 1ull << 26);  // <= 256 MiB staging
     void* stage = nullptr;
@@ -2061,11 +2096,11 @@ static int vox_xfer(semtsdf_vol* v, void* host, void* dev, bool to_host, const c
         char* h = static_cast<char*>(host) + (v0 - vb) * 4;
         hipError_t e;
         if (to_host) {
-            e = launch_vox_chunk(dev, stage, true, v->g, v0, nv, s);
+            e = launch_vox_chunk(dev, stage, true, v->g, v0, nv, s, dev_u16);
             if (e == hipSuccess) e = hipMemcpyAsync(h, stage, nv * 4, hipMemcpyDeviceToHost, s);
         } else {
             e = hipMemcpyAsync(stage, h, nv * 4, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = launch_vox_chunk(stage, dev, false, v->g, v0, nv, s);
+            if (e == hipSuccess) e = launch_vox_chunk(stage, dev, false, v->g, v0, nv, s, dev_u16);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) {
@@ -2116,7 +2151,7 @@ int semtsdf_download_slab(semtsdf_vol* v, int x0, int x1, float* sdf, int32_t* w
     const uint64_t vb = (uint64_t)x0 * plane, ve = (uint64_t)x1 * plane;
     int rc;
     if (sdf && (rc = vox_xfer(v, sdf, v->b.sdf, true, "sdf", s, vb, ve))) return rc;
-    if (wt && (rc = vox_xfer(v, wt, v->b.wt, true, "weight", s, vb, ve))) return rc;
+    if (wt && (rc = vox_xfer(v, wt, v->b.wt, true, "weight", s, vb, ve, !v->wt_wide))) return rc;
     if (color) {
         rc = color_xfer(v, color, true, s, vb, ve);
         if (rc) return rc;
@@ -2169,11 +2204,13 @@ int semtsdf_upload(semtsdf_vol* v, const float* sdf, const int32_t* wt, const vo
     v->maps_stale = true;
     if (sdf || wt) HIPC(hipMemsetAsync(v->b.sflag, 0, v->g.nvox / 32 + 1, s));  // steady flags: unknown
     if (sdf && (rc = vox_xfer(v, const_cast<float*>(sdf), v->b.sdf, false, "sdf", s, 0, nref(v)))) return rc;
-    if (wt && (rc = vox_xfer(v, const_cast<int32_t*>(wt), v->b.wt, false, "weight", s, 0, nref(v)))) return rc;
     if (wt) {
-        int64_t m = 0;
-        for (uint64_t i = 0, n = nref(v); i < n; ++i) m = std::max<int64_t>(m, wt[i]);
-        v->wmax_bound = m;
+        // one pass over the values: their upper bound, and whether uint16 storage holds them all
+        const WeightScan ws = scan_weights(wt, nref(v));
+        if (!ws.fits_u16 && (rc = widen_weights(v, s))) return rc;
+        rc = vox_xfer(v, const_cast<int32_t*>(wt), v->b.wt, false, "weight", s, 0, nref(v), !v->wt_wide);
+        if (rc) return rc;
+        v->wmax_bound = ws.wmax;
     }
     if (color) {
         if ((v->p.flags & SEMTSDF_F_COLOR_I32) && !v->color_wide) {

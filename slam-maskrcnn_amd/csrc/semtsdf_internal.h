@@ -61,7 +61,9 @@ __device__ inline uint32_t tile_index(const VolGeom& g, int x, int y, int zl) {
 // Device buffers of one volume.
 struct VolBufs {
     float* sdf;
-    int32_t* wt;
+    void* wt;          // u16 per voxel, or i32 once a weight could pass 65535 (wt_wide; see
+                       // semtsdf_vol::wt_wide), same tiled layout: a lane's 4 z-neighbours are one
+                       // 8-B (16-B) vector
     void* color;       // u8x4 or i32x4 per voxel (3 channels + pad)
     uint32_t* hist;    // bin-major [32][nvox]
     uint32_t* hmask;   // [nvox] bit k set when hist[k][v] > 0 (kept by the integrate; samplers
@@ -81,7 +83,13 @@ struct VolBufs {
     uint32_t* dlist;   // [1 + quads]: count, then the quads whose dirty word is nonzero
     uint8_t* sflag;    // per 128-B sdf line (32 voxels): s >= 1 = every sdf is 1.0f and every weight
                        // < 2^23 (k_integrate skips the sdf traffic of such lines); 0 = unknown
+    int wt_wide;       // wt holds int32_t (else uint16_t)
 };
+
+// Weight of the voxel at tiled index t, in either storage form.
+__device__ inline int wt_at(const VolBufs& b, uint32_t t) {
+    return b.wt_wide ? static_cast<const int32_t*>(b.wt)[t] : (int)static_cast<const uint16_t*>(b.wt)[t];
+}
 
 // Per-frame images of the integrate: depth in metres and rgb+label per pixel (row-major,
 // W x H), and per 8- and 32-pixel tile the max raw depth (bits 0-15) and 0xFFFF - the min
@@ -378,7 +386,8 @@ hipError_t launch_depth_pyramid(const uint16_t* depth, const uint8_t* rgb, uint8
                                 float scale, const DepthPyramid& p, unsigned* list_count, hipStream_t s,
                                 const uint8_t* lut = nullptr);  // lut: relabel the mask in place (k_relabel folded in)
 hipError_t launch_vox_chunk(const void* src, void* dst, bool to_ref, const VolGeom& g, uint64_t v0, uint64_t nv,
-                            hipStream_t s);
+                            hipStream_t s, bool dev_u16 = false);  // dev_u16: the device array holds uint16_t
+hipError_t launch_weight_widen(const uint16_t* narrow, int32_t* wide, uint64_t nvox, hipStream_t s);  // u16 -> i32
 hipError_t launch_color_widen(const uint8_t* narrow, int32_t* wide, uint64_t nvox, hipStream_t s);  // u8x4 -> i32x4
 hipError_t launch_color_chunk(const void* src, void* dst, bool to_ref, bool ref_i32, bool dev_i32, const VolGeom& g,
                               uint64_t v0, uint64_t nv, hipStream_t s);

@@ -1287,13 +1287,31 @@ __device__ __forceinline__ void st_state(void* p, const T& v) {
     static_assert(sizeof(T) == 16, "16-byte vectors");
     *reinterpret_cast<T*>(p) = v;
 }
+// The lane's four weights at element offset v: one 16-B vector of int32 (WW), or one 8-B vector
+// of uint16 unpacked into the same int4 (narrow storage holds values <= 65535 only:
+// semtsdf_api.cpp, widen_weights)
+template <bool WW>
+__device__ __forceinline__ int4 ld_weights(const void* wt, uint32_t v) {
+    if (WW) return ld_state<int4>(static_cast<const int32_t*>(wt) + v);
+    const uint2 p = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(wt) + v);
+    return make_int4((int)(p.x & 0xFFFFu), (int)(p.x >> 16), (int)(p.y & 0xFFFFu), (int)(p.y >> 16));
+}
+template <bool WW>
+__device__ __forceinline__ void st_weights(void* wt, uint64_t v, const int4& w) {
+    if (WW) {
+        st_state(static_cast<int32_t*>(wt) + v, w);
+    } else {
+        *reinterpret_cast<uint2*>(static_cast<uint16_t*>(wt) + v) =
+            make_uint2((unsigned)w.x | ((unsigned)w.y << 16), (unsigned)w.z | ((unsigned)w.w << 16));
+    }
+}
 
 // Unconditional loads: a lane with nothing to load reads the dummy line (one 16-B vector
 // shared by all such lanes), so the issue count is the same on every path.  The dummy line
 // is the array's first vector (offset 0, selected in 32 bits: one base pointer per array),
 // which stays in L2 like a steady line (the unit's first line instead was an extra line
 // fetched whenever that line itself has no update: DESIGN.md §3, "r06: traffic").
-template <bool SEM, bool CI32, bool VOTE, bool FREE>
+template <bool SEM, bool CI32, bool VOTE, bool FREE, bool WW>
 __device__ __forceinline__ void stage_load(const IntegrateArgs& a, const UnitPos& up, unsigned coff, const Cls& C,
                                            Ld& L) {
     const VolGeom& g = a.g;
@@ -1313,7 +1331,7 @@ __device__ __forceinline__ void stage_load(const IntegrateArgs& a, const UnitPos
     const bool skip = (C.sflag != 0u) & fone;  // each lane for itself
     L.skip = skip;
     L.s4 = ld_state<float4>(a.b.sdf + ((skip | !t) ? 0u : v));
-    L.w4 = ld_state<int4>(a.b.wt + (t ? v : 0u));
+    L.w4 = ld_weights<WW>(a.b.wt, t ? v : 0u);
     if (FREE) return;  // sdf and weight only
     if (CI32) {
 #pragma unroll
@@ -1468,7 +1486,7 @@ __device__ __forceinline__ void voxel_add(uint32_t* p, uint32_t v) {
     (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-template <bool SEM, bool CI32, bool VOTE, bool FREE>
+template <bool SEM, bool CI32, bool VOTE, bool FREE, bool WW>
 __device__ __forceinline__ void stage_store(const IntegrateArgs& a, const UnitPos& up, unsigned coff,
                                             const StoreMeta& M, const Out& O) {
     const VolGeom& g = a.g;
@@ -1512,7 +1530,7 @@ __device__ __forceinline__ void stage_store(const IntegrateArgs& a, const UnitPo
     const uint64_t v = O.ub + coff;
     if (!(kProbes && a.debug == 10) && tmask != 0u) {  // 10: timing probe, loads but no sdf/weight stores
         if (!O.skip) st_state(a.b.sdf + v, O.s4);
-        st_state(a.b.wt + v, O.w4);
+        st_weights<WW>(a.b.wt, v, O.w4);
     }
     {  // the line's flag byte after this update (one lane per line writes)
         // every sdf exactly 1.0f (bits: AND and OR of the four both equal 1.0f's) and every weight < 2^23
@@ -1663,7 +1681,7 @@ struct KindOf {
 };
 
 // The project / classify / load stages of the wave's first group of list v (v.i < v.ngroups).
-template <bool SEM, bool GATE, bool CI32, bool VOTE, bool COUNT, bool SHARD, bool PIN, int KIND>
+template <bool SEM, bool GATE, bool CI32, bool VOTE, bool WW, bool COUNT, bool SHARD, bool PIN, int KIND>
 __device__ __forceinline__ void list_prime(const IntegrateArgs& a, const UnitGrid& ug, unsigned seg_cap,
                                            const ListView& v, Pipe& S, Counts& n, const unsigned* pre = nullptr) {
     constexpr bool FREE = KindOf<KIND>::FREE, FULL = KindOf<KIND>::FULL;
@@ -1679,7 +1697,7 @@ __device__ __forceinline__ void list_prime(const IntegrateArgs& a, const UnitGri
     S.cur = lane_pos(ug, e);
     stage_project<SHARD, PIN, FREE, FULL, VOTE>(a, S.cur, lane, S.P);
     stage_classify<SEM, GATE, VOTE, COUNT, FREE>(a, S.P, S.C, true, n.touch, n.gate, n.lines, S.lutv);
-    stage_load<SEM, CI32, VOTE, FREE>(a, S.cur, coff, S.C, S.L);
+    stage_load<SEM, CI32, VOTE, FREE, WW>(a, S.cur, coff, S.C, S.L);
     S.primed = true;
 }
 
@@ -1711,7 +1729,7 @@ __device__ __forceinline__ unsigned dispatch_round() {
 // the list is computed and stored under the project / classify / load of its first unit of
 // the next list (kind NKIND, `nx`; NKIND < 0: none), which then starts primed: the pipeline
 // does not drain and refill between the lists.
-template <bool SEM, bool GATE, bool CI32, bool VOTE, bool COUNT, bool SHARD, bool PIN, int KIND, int NKIND>
+template <bool SEM, bool GATE, bool CI32, bool VOTE, bool WW, bool COUNT, bool SHARD, bool PIN, int KIND, int NKIND>
 __device__ __forceinline__ void integrate_list(const IntegrateArgs& a, const UnitGrid& ug, unsigned seg_cap,
                                                const float* __restrict__ s_rcp, ListView& v, const ListView* nx,
                                                unsigned nwaves, Pipe& S, Counts& n) {
@@ -1723,7 +1741,7 @@ __device__ __forceinline__ void integrate_list(const IntegrateArgs& a, const Uni
     // no group of this list for the wave: the next list primes itself (a primed pipeline
     // always holds a unit of the first list, in order, that has a group for the wave)
     if (v.i >= v.ngroups) return;
-    if (!S.primed) list_prime<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, KIND>(a, ug, seg_cap, v, S, n);
+    if (!S.primed) list_prime<SEM, GATE, CI32, VOTE, WW, COUNT, SHARD, PIN, KIND>(a, ug, seg_cap, v, S, n);
     unsigned en[kSlots];
     if (v.i + nwaves < v.ngroups) group_entries(v, v.i + nwaves, seg_cap, en);
     const bool chain = NKIND >= 0 && nx->i < nx->ngroups;
@@ -1736,8 +1754,8 @@ __device__ __forceinline__ void integrate_list(const IntegrateArgs& a, const Uni
         stage_compute<SEM, GATE, CI32, VOTE, FREE>(a, s_rcp, S.C, S.L, S.O);
         const StoreMeta Mc = store_meta(S.C);
         stage_classify<SEM, GATE, VOTE, COUNT, FREE>(a, S.P, S.C, true, n.touch, n.gate, n.lines, S.lutv);
-        stage_store<SEM, CI32, VOTE, FREE>(a, S.cur, coff, Mc, S.O);
-        stage_load<SEM, CI32, VOTE, FREE>(a, nxt, coff, S.C, S.L);
+        stage_store<SEM, CI32, VOTE, FREE, WW>(a, S.cur, coff, Mc, S.O);
+        stage_load<SEM, CI32, VOTE, FREE, WW>(a, nxt, coff, S.C, S.L);
         S.cur = nxt;
         v.i += nwaves;
         // the wave's group counter (no division by nwaves in the loop): a priority step every
@@ -1753,13 +1771,13 @@ __device__ __forceinline__ void integrate_list(const IntegrateArgs& a, const Uni
         stage_compute<SEM, GATE, CI32, VOTE, FREE>(a, s_rcp, S.C, S.L, S.O);
         const StoreMeta Mc = store_meta(S.C);
         stage_classify<SEM, GATE, VOTE, COUNT, NFREE>(a, S.P, S.C, true, n.touch, n.gate, n.lines, S.lutv);
-        stage_store<SEM, CI32, VOTE, FREE>(a, S.cur, coff, Mc, S.O);
-        stage_load<SEM, CI32, VOTE, NFREE>(a, nxt, coff, S.C, S.L);
+        stage_store<SEM, CI32, VOTE, FREE, WW>(a, S.cur, coff, Mc, S.O);
+        stage_load<SEM, CI32, VOTE, NFREE, WW>(a, nxt, coff, S.C, S.L);
         S.cur = nxt;
         S.primed = true;
     } else {
         stage_compute<SEM, GATE, CI32, VOTE, FREE>(a, s_rcp, S.C, S.L, S.O);
-        stage_store<SEM, CI32, VOTE, FREE>(a, S.cur, coff, store_meta(S.C), S.O);
+        stage_store<SEM, CI32, VOTE, FREE, WW>(a, S.cur, coff, store_meta(S.C), S.O);
         S.primed = false;
     }
     v.i += nwaves;
@@ -1775,10 +1793,11 @@ __device__ __forceinline__ void integrate_list(const IntegrateArgs& a, const Uni
 #ifndef SEMTSDF_INTEGRATE_WPE
 #define SEMTSDF_INTEGRATE_WPE 4  // waves per SIMD the register allocation targets (5 spills; measured equal)
 #endif
-template <bool SEM, bool GATE, bool CI32, bool VOTE, bool COUNT, bool SHARD, bool PIN>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VOTE ? 3 : SEMTSDF_INTEGRATE_WPE))) void k_integrate(
-    IntegrateArgs a, UnitGrid ug, unsigned seg_cap) {
-    __shared__ float s_rcp[kRcpTable];
+// The kernel's body with the weight storage form WW (int32, else uint16) as a compile-time
+// parameter; k_integrate (uint16 weights) and k_integrate_w (int32 weights) below instantiate it.
+template <bool SEM, bool GATE, bool CI32, bool VOTE, bool WW, bool COUNT, bool SHARD, bool PIN>
+__device__ __forceinline__ void integrate_body(const IntegrateArgs& a, const UnitGrid& ug, unsigned seg_cap,
+                                               float* s_rcp) {
     // instrumentation: per-wave wall-clock marks (entry, table loaded, after each list) and
     // the wave's group counts per list
     unsigned long long tr[5] = {0, 0, 0, 0, 0};
@@ -1828,22 +1847,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VOTE ? 3 : 
         rot0 = (vf.cnt + v1.cnt) % nwx;
         ListView v0 = list_view(lst, cnt, 0, wx, nwx, rot0, xi, nsp);
         if (vf.i < vf.ngroups)
-            list_prime<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, 2>(a, ug, seg_cap, vf, S, n);
+            list_prime<SEM, GATE, CI32, VOTE, WW, COUNT, SHARD, PIN, 2>(a, ug, seg_cap, vf, S, n);
         else if (v1.i < v1.ngroups)
-            list_prime<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, 1>(a, ug, seg_cap, v1, S, n,
+            list_prime<SEM, GATE, CI32, VOTE, WW, COUNT, SHARD, PIN, 1>(a, ug, seg_cap, v1, S, n,
                                                                    (!split || tab) && wq == wave ? pre1 : nullptr);
         else if (v0.i < v0.ngroups)
-            list_prime<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, 0>(a, ug, seg_cap, v0, S, n);
+            list_prime<SEM, GATE, CI32, VOTE, WW, COUNT, SHARD, PIN, 0>(a, ug, seg_cap, v0, S, n);
         __syncthreads();
         if (SEMTSDF_WAVE_TRACE) tr[1] = tr[2] = tr[3] = wall_clock64();
-        integrate_list<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, 2, 1>(a, ug, seg_cap, s_rcp, vf, &v1, nwx, S, n);
+        integrate_list<SEM, GATE, CI32, VOTE, WW, COUNT, SHARD, PIN, 2, 1>(a, ug, seg_cap, s_rcp, vf, &v1, nwx, S, n);
         if (SEMTSDF_WAVE_TRACE) tr[2] = wall_clock64();
-        integrate_list<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, 1, 0>(a, ug, seg_cap, s_rcp, v1, &v0, nwx, S, n);
+        integrate_list<SEM, GATE, CI32, VOTE, WW, COUNT, SHARD, PIN, 1, 0>(a, ug, seg_cap, s_rcp, v1, &v0, nwx, S, n);
         if (SEMTSDF_WAVE_TRACE) {
             tr[3] = wall_clock64();
             trn = groups_of(vf.total, 0u) | (groups_of(v1.total, 0u) << 20);
         }
-        integrate_list<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, 0, -1>(a, ug, seg_cap, s_rcp, v0, nullptr, nwx, S, n);
+        integrate_list<SEM, GATE, CI32, VOTE, WW, COUNT, SHARD, PIN, 0, -1>(a, ug, seg_cap, s_rcp, v0, nullptr, nwx, S, n);
         n0 = v0.total;
         if (COUNT && blockIdx.x == 0 && threadIdx.x == 0) {
             atomicAdd(a.counters + 4, (unsigned long long)(v1.total + vf.total));
@@ -1862,12 +1881,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VOTE ? 3 : 
         const unsigned pre0[2] = {t4[4u + 2u * wq], t4[5u + 2u * wq]};
         ListView v0 = list_view(lst, cnt, 0, wx, nwx, 0u, xi, nsp);
         if (v0.i < v0.ngroups)
-            list_prime<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, 0>(a, ug, seg_cap, v0, S, n,
+            list_prime<SEM, GATE, CI32, VOTE, WW, COUNT, SHARD, PIN, 0>(a, ug, seg_cap, v0, S, n,
                                                                    (tab || (!split && v0.list == lst + 4)) && wq == wave ? pre0
                                                                                                                 : nullptr);
         __syncthreads();
         if (SEMTSDF_WAVE_TRACE) tr[1] = tr[2] = tr[3] = wall_clock64();
-        integrate_list<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN, 0, -1>(a, ug, seg_cap, s_rcp, v0, nullptr, nwx, S, n);
+        integrate_list<SEM, GATE, CI32, VOTE, WW, COUNT, SHARD, PIN, 0, -1>(a, ug, seg_cap, s_rcp, v0, nullptr, nwx, S, n);
         n0 = v0.total;
     }
     if (SEM && a.lut && a.relabel_mask) {  // the frame's mask through the same table, in place
@@ -1920,6 +1939,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VOTE ? 3 : 
     }
 }
 
+template <bool SEM, bool GATE, bool CI32, bool VOTE, bool COUNT, bool SHARD, bool PIN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VOTE ? 3 : SEMTSDF_INTEGRATE_WPE))) void k_integrate(
+    IntegrateArgs a, UnitGrid ug, unsigned seg_cap) {
+    __shared__ float s_rcp[kRcpTable];
+    integrate_body<SEM, GATE, CI32, VOTE, false, COUNT, SHARD, PIN>(a, ug, seg_cap, s_rcp);
+}
+
+// The same over int32 weights (a volume whose weights could pass 65535: widen_weights).
+template <bool SEM, bool GATE, bool CI32, bool VOTE, bool COUNT, bool SHARD, bool PIN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VOTE ? 3 : SEMTSDF_INTEGRATE_WPE))) void k_integrate_w(
+    IntegrateArgs a, UnitGrid ug, unsigned seg_cap) {
+    __shared__ float s_rcp[kRcpTable];
+    integrate_body<SEM, GATE, CI32, VOTE, true, COUNT, SHARD, PIN>(a, ug, seg_cap, s_rcp);
+}
+
 // Persistent grid sized to exactly the resident capacity (blocks/CU from the occupancy
 // query x CUs): an oversubscribed persistent grid leaves a tail of late blocks.
 static unsigned resident_grid_cus() {
@@ -1938,7 +1972,7 @@ static unsigned resident_grid(K kernel, int block = 256) {
     return (unsigned)(cus * per);
 }
 
-template <bool SEM, bool GATE, bool CI32, bool VOTE, bool COUNT, bool SHARD, bool PIN>
+template <bool SEM, bool GATE, bool CI32, bool VOTE, bool WW, bool COUNT, bool SHARD, bool PIN>
 static hipError_t launch_integrate_k(const IntegrateArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     const UnitGrid ug = unit_grid(a.g);
     if (ug.n == 0) return hipSuccess;
@@ -1946,46 +1980,49 @@ static hipError_t launch_integrate_k(const IntegrateArgs& a, hipStream_t s, hipE
     // past residency (the occupancy query can over-report, MI355X_MICROARCH.md) only adds
     // late waves with the same share
     constexpr int block = 256;
-    static const unsigned grid0 = resident_grid(k_integrate<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN>, block);
+    const auto kern = WW ? k_integrate_w<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN>
+                         : k_integrate<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN>;
+    static const unsigned grid0 = resident_grid(kern, block);
     const unsigned ncu = resident_grid_cus();
     unsigned grid = grid0;
     if (kProbes && a.debug >= 100) grid = grid0 * (unsigned)(a.debug - 100) / 8u;  // probe: fraction of residency
     static const char* gpc = getenv("SEMTSDF_GRID_PER_CU");              // probe: blocks per CU
     if (gpc && atoi(gpc) > 0) grid = ncu * (unsigned)atoi(gpc);
     if (e0) {  // timing: events recorded by the dispatch itself (kernel start / end)
-        hipExtLaunchKernelGGL((k_integrate<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN>), dim3(grid), dim3(block), 0, s, e0,
+        hipExtLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, s, e0,
                               e1, 0, a, ug, list_seg_cap(ug));
     } else {
-        hipLaunchKernelGGL((k_integrate<SEM, GATE, CI32, VOTE, COUNT, SHARD, PIN>), dim3(grid), dim3(block), 0, s, a, ug,
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, s, a, ug,
                            list_seg_cap(ug));
     }
     return hipGetLastError();
 }
 
-template <bool SEM, bool GATE, bool CI32, bool VOTE>
+template <bool SEM, bool GATE, bool CI32, bool VOTE, bool WW>
 static hipError_t launch_integrate_t(const IntegrateArgs& a, bool count, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     const bool shard = a.g.nshards > 1, pin = a.pinhole != 0;
     if (count) {  // measurement pass: pinhole only is not assumed
-        if (shard) return launch_integrate_k<SEM, GATE, CI32, VOTE, true, true, false>(a, s, e0, e1);
-        return launch_integrate_k<SEM, GATE, CI32, VOTE, true, false, false>(a, s, e0, e1);
+        if (shard) return launch_integrate_k<SEM, GATE, CI32, VOTE, WW, true, true, false>(a, s, e0, e1);
+        return launch_integrate_k<SEM, GATE, CI32, VOTE, WW, true, false, false>(a, s, e0, e1);
     }
     if (shard) {
-        if (pin) return launch_integrate_k<SEM, GATE, CI32, VOTE, false, true, true>(a, s, e0, e1);
-        return launch_integrate_k<SEM, GATE, CI32, VOTE, false, true, false>(a, s, e0, e1);
+        if (pin) return launch_integrate_k<SEM, GATE, CI32, VOTE, WW, false, true, true>(a, s, e0, e1);
+        return launch_integrate_k<SEM, GATE, CI32, VOTE, WW, false, true, false>(a, s, e0, e1);
     }
-    if (pin) return launch_integrate_k<SEM, GATE, CI32, VOTE, false, false, true>(a, s, e0, e1);
-    return launch_integrate_k<SEM, GATE, CI32, VOTE, false, false, false>(a, s, e0, e1);
+    if (pin) return launch_integrate_k<SEM, GATE, CI32, VOTE, WW, false, false, true>(a, s, e0, e1);
+    return launch_integrate_k<SEM, GATE, CI32, VOTE, WW, false, false, false>(a, s, e0, e1);
 }
 
 unsigned integrate_pre_waves() {
-    // the SfM semantic instantiation (the others run at the same occupancy; where one does not, its
-    // waves read their first group the ordinary way: k_integrate compares first_nwaves with its grid)
+    // the SfM semantic instantiation over u16 weights (the others run at the same occupancy; where one does not,
+    // its waves read their first group the ordinary way: k_integrate compares first_nwaves with its grid)
     static const unsigned w = 4u * resident_grid(k_integrate<true, true, false, false, false, false, true>, 256);
     // a grid with more wave slots than k_compact_lists writes gets no table (0: read the ordinary way)
     return w <= kFirstTabSlots ? w : 0u;
 }
 
-hipError_t launch_integrate(const IntegrateArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+template <bool WW>
+static hipError_t launch_integrate_w(const IntegrateArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     const bool count = a.counters != nullptr && (a.flags & 0x80000000u);
     // ci32: the colour STORAGE is int32 x 4 (a COLOR_I32 volume holding values outside [0, 255]);
     // a COLOR_I32 volume whose colours fit a byte stores them as u8 x 4 and integrates them
@@ -1994,23 +2031,28 @@ hipError_t launch_integrate(const IntegrateArgs& a, hipStream_t s, hipEvent_t e0
     // Instantiated mode combinations: SfM semantic (u8 colour, gated), TSDF+colour (NumPy
     // rule: i32 colour, ungated), TSDF_Python vote, plus their neighbours.
     if (vote) {
-        if (ci32) return launch_integrate_t<false, false, true, true>(a, count, s, e0, e1);
-        return launch_integrate_t<false, false, false, true>(a, count, s, e0, e1);
+        if (ci32) return launch_integrate_t<false, false, true, true, WW>(a, count, s, e0, e1);
+        return launch_integrate_t<false, false, false, true, WW>(a, count, s, e0, e1);
     }
     if (sem) {
         if (gate) {
-            if (ci32) return launch_integrate_t<true, true, true, false>(a, count, s, e0, e1);
-            return launch_integrate_t<true, true, false, false>(a, count, s, e0, e1);
+            if (ci32) return launch_integrate_t<true, true, true, false, WW>(a, count, s, e0, e1);
+            return launch_integrate_t<true, true, false, false, WW>(a, count, s, e0, e1);
         }
-        if (ci32) return launch_integrate_t<true, false, true, false>(a, count, s, e0, e1);
-        return launch_integrate_t<true, false, false, false>(a, count, s, e0, e1);
+        if (ci32) return launch_integrate_t<true, false, true, false, WW>(a, count, s, e0, e1);
+        return launch_integrate_t<true, false, false, false, WW>(a, count, s, e0, e1);
     }
     if (gate) {
-        if (ci32) return launch_integrate_t<false, true, true, false>(a, count, s, e0, e1);
-        return launch_integrate_t<false, true, false, false>(a, count, s, e0, e1);
+        if (ci32) return launch_integrate_t<false, true, true, false, WW>(a, count, s, e0, e1);
+        return launch_integrate_t<false, true, false, false, WW>(a, count, s, e0, e1);
     }
-    if (ci32) return launch_integrate_t<false, false, true, false>(a, count, s, e0, e1);
-    return launch_integrate_t<false, false, false, false>(a, count, s, e0, e1);
+    if (ci32) return launch_integrate_t<false, false, true, false, WW>(a, count, s, e0, e1);
+    return launch_integrate_t<false, false, false, false, WW>(a, count, s, e0, e1);
+}
+
+hipError_t launch_integrate(const IntegrateArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+    // the weight storage (u16, or int32 once a weight could pass 65535) is a compile-time parameter
+    return a.b.wt_wide ? launch_integrate_w<true>(a, s, e0, e1) : launch_integrate_w<false>(a, s, e0, e1);
 }
 
 // ------------------------------------------------------------------------------------
@@ -3458,9 +3500,10 @@ hipError_t launch_render(const RenderArgs& a, hipStream_t s) {
 __device__ __forceinline__ float maps_sample(const VolGeom& g, const VolBufs& b, float px, float py, float pz,
                                              int* wmin) {
     const Tri tr = tri_setup<false>(g, px, py, pz);
-    const int32_t* q = b.wt + tr.i000;
-    const int w0 = min(min(q[0], q[tr.dz]), min(q[tr.dy], q[tr.dy + tr.dz]));
-    const int w1 = min(min(q[tr.dx], q[tr.dx + tr.dz]), min(q[tr.dx + tr.dy], q[tr.dx + tr.dy + tr.dz]));
+    const uint32_t q = tr.i000;
+    const int w0 = min(min(wt_at(b, q), wt_at(b, q + tr.dz)), min(wt_at(b, q + tr.dy), wt_at(b, q + tr.dy + tr.dz)));
+    const int w1 = min(min(wt_at(b, q + tr.dx), wt_at(b, q + tr.dx + tr.dz)),
+                       min(wt_at(b, q + tr.dx + tr.dy), wt_at(b, q + tr.dx + tr.dy + tr.dz)));
     *wmin = min(*wmin, min(w0, w1));
     return tri_eval(b.sdf, tr);
 }
@@ -4215,28 +4258,36 @@ hipError_t launch_hist_chunk_to_bm(const uint32_t* vm, uint32_t* bm, const VolGe
     return hipGetLastError();
 }
 
-// 4-byte per-voxel arrays (sdf, weight, vote label/count): tiled device <-> reference rows
-__global__ __launch_bounds__(256) void k_vox_to_ref(VolGeom g, const uint32_t* __restrict__ dev, uint32_t* __restrict__ ref,
+// 4-byte per-voxel arrays (sdf, weight, vote label/count): tiled device <-> reference rows.
+// TD: the device element (uint16_t: narrow weights, zero-extended to the boundary's int32; the
+// host checked that an upload's values fit, semtsdf_upload)
+template <typename TD>
+__global__ __launch_bounds__(256) void k_vox_to_ref(VolGeom g, const TD* __restrict__ dev, uint32_t* __restrict__ ref,
                                                     uint64_t v0, uint64_t nv) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (uint64_t)gridDim.x * blockDim.x)
         ref[i] = dev[tile_of_ref(g, v0 + i)];
 }
 
-__global__ __launch_bounds__(256) void k_vox_from_ref(VolGeom g, const uint32_t* __restrict__ ref, uint32_t* __restrict__ dev,
+template <typename TD>
+__global__ __launch_bounds__(256) void k_vox_from_ref(VolGeom g, const uint32_t* __restrict__ ref, TD* __restrict__ dev,
                                                       uint64_t v0, uint64_t nv) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (uint64_t)gridDim.x * blockDim.x)
-        dev[tile_of_ref(g, v0 + i)] = ref[i];
+        dev[tile_of_ref(g, v0 + i)] = (TD)ref[i];
 }
 
 hipError_t launch_vox_chunk(const void* src, void* dst, bool to_ref, const VolGeom& g, uint64_t v0, uint64_t nv,
-                            hipStream_t s) {
+                            hipStream_t s, bool dev_u16) {
     uint64_t blocks = (nv + 255) / 256;
     if (blocks > 16384) blocks = 16384;
     if (blocks == 0) return hipSuccess;
-    if (to_ref)
-        hipLaunchKernelGGL(k_vox_to_ref, dim3((unsigned)blocks), dim3(256), 0, s, g, (const uint32_t*)src, (uint32_t*)dst, v0, nv);
+    if (to_ref && dev_u16)
+        hipLaunchKernelGGL(k_vox_to_ref<uint16_t>, dim3((unsigned)blocks), dim3(256), 0, s, g, (const uint16_t*)src, (uint32_t*)dst, v0, nv);
+    else if (to_ref)
+        hipLaunchKernelGGL(k_vox_to_ref<uint32_t>, dim3((unsigned)blocks), dim3(256), 0, s, g, (const uint32_t*)src, (uint32_t*)dst, v0, nv);
+    else if (dev_u16)
+        hipLaunchKernelGGL(k_vox_from_ref<uint16_t>, dim3((unsigned)blocks), dim3(256), 0, s, g, (const uint32_t*)src, (uint16_t*)dst, v0, nv);
     else
-        hipLaunchKernelGGL(k_vox_from_ref, dim3((unsigned)blocks), dim3(256), 0, s, g, (const uint32_t*)src, (uint32_t*)dst, v0, nv);
+        hipLaunchKernelGGL(k_vox_from_ref<uint32_t>, dim3((unsigned)blocks), dim3(256), 0, s, g, (const uint32_t*)src, (uint32_t*)dst, v0, nv);
     return hipGetLastError();
 }
 
@@ -4267,6 +4318,20 @@ __global__ __launch_bounds__(256) void k_color_widen(const uint32_t* __restrict_
         const uint32_t c = narrow[v];
         wide[v] = make_int4((int)(c & 0xFFu), (int)((c >> 8) & 0xFFu), (int)((c >> 16) & 0xFFu), 0);
     }
+}
+
+__global__ __launch_bounds__(256) void k_weight_widen(const uint16_t* __restrict__ narrow, int32_t* __restrict__ wide,
+                                                      uint64_t nvox) {
+    for (uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvox; v += (uint64_t)gridDim.x * blockDim.x)
+        wide[v] = (int32_t)narrow[v];
+}
+
+hipError_t launch_weight_widen(const uint16_t* narrow, int32_t* wide, uint64_t nvox, hipStream_t s) {
+    if (nvox == 0) return hipSuccess;
+    uint64_t blocks = (nvox + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(k_weight_widen, dim3((unsigned)blocks), dim3(256), 0, s, narrow, wide, nvox);
+    return hipGetLastError();
 }
 
 hipError_t launch_color_widen(const uint8_t* narrow, int32_t* wide, uint64_t nvox, hipStream_t s) {
@@ -4589,7 +4654,7 @@ __global__ __launch_bounds__(256) void k_export_surface(VolGeom g, VolBufs b, fl
         const int gz = local_to_global_z(g, l);
         if (gz >= g.dimz) continue;
         const uint32_t t = tile_index(g, x, y, l);
-        const int w = b.wt[t];
+        const int w = wt_at(b, t);
         const float s = b.sdf[t];
         if (w < min_w || !(fabsf(s) < sdf_max)) continue;
         unsigned r, gg, bb;
@@ -4797,7 +4862,7 @@ __global__ __launch_bounds__(256) void k_mesh_classify(VolGeom g, VolBufs b, int
             local_to_global_z(g, L) < g.dimz) {
             const uint32_t t = tile_index(g, X, Y, L);
             s = b.sdf[t];
-            const unsigned ok = b.wt[t] >= min_w ? 1u : 0u, ng = s < 0.0f ? 1u : 0u;
+            const unsigned ok = wt_at(b, t) >= min_w ? 1u : 0u, ng = s < 0.0f ? 1u : 0u;
             f = ok | (ng << 1);
             has_neg |= (int)(ok & ng);
             has_pos |= (int)(ok & (ng ^ 1u));
@@ -5040,7 +5105,13 @@ __global__ __launch_bounds__(256) void k_instance_stats(VolGeom g, VolBufs b, fl
          tile += gridDim.x * 4u) {
         const uint32_t t0 = tile * 256u + lane * 4u;
         const float4 s4 = reinterpret_cast<const float4*>(b.sdf)[t0 >> 2];
-        const int4 w4 = reinterpret_cast<const int4*>(b.wt)[t0 >> 2];
+        int4 w4;  // the lane's 4 weights: one 16-B vector, or 8 B of u16
+        if (b.wt_wide) {
+            w4 = reinterpret_cast<const int4*>(b.wt)[t0 >> 2];
+        } else {
+            const uint2 p = reinterpret_cast<const uint2*>(b.wt)[t0 >> 2];
+            w4 = make_int4((int)(p.x & 0xFFFFu), (int)(p.x >> 16), (int)(p.y & 0xFFFFu), (int)(p.y >> 16));
+        }
         const float sv[4] = {s4.x, s4.y, s4.z, s4.w};
         const int wv[4] = {w4.x, w4.y, w4.z, w4.w};
         unsigned sel = 0;

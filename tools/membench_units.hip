@@ -4,7 +4,11 @@
 //   xrun    x fastest (the cull grid's order today: consecutive units 1 MiB apart at 512^3)
 //   zrun    z fastest (consecutive units adjacent in memory)
 //   random  shuffled
-// Reports GB/s of (sdf + weight) r+w bytes.  Build: hipcc --offload-arch=gfx950 -O3 tools/membench_units.hip -o tools/membench_units
+// and in three state forms:
+//   i32     sdf f32 + weight i32 (16 B + 16 B per lane)
+//   u16     sdf f32 + weight u16 (16 B + 8 B per lane)
+//   u16only weight u16 alone (8 B per lane: the steady-line case, sdf neither read nor written)
+// Reports GB/s of the form's r+w bytes.  Build: hipcc --offload-arch=gfx950 -O3 tools/membench_units.hip -o tools/membench_units
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,6 +36,8 @@ __host__ __device__ inline size_t unit_base(unsigned u) {
     return ((size_t)x * NUY * NUZ + (size_t)uy * NUZ + uz) * 128u;
 }
 
+typedef unsigned short h4 __attribute__((ext_vector_type(4)));
+template <int FORM>
 __global__ __launch_bounds__(256) void k_rmw(float* __restrict__ sdf, int* __restrict__ wt, const unsigned* __restrict__ list,
                                              unsigned n) {
     const unsigned lane = threadIdx.x & 63u;
@@ -41,12 +47,21 @@ __global__ __launch_bounds__(256) void k_rmw(float* __restrict__ sdf, int* __res
         const unsigned i = 2u * g + (lane >> 5);
         if (i >= n) continue;
         const size_t v = unit_base(list[i]) + (lane & 31u) * 4u;
-        f4 s = __builtin_nontemporal_load(reinterpret_cast<f4*>(sdf + v));
-        i4 w = __builtin_nontemporal_load(reinterpret_cast<i4*>(wt + v));
-        s += 1.f;
-        w += 1;
-        __builtin_nontemporal_store(s, reinterpret_cast<f4*>(sdf + v));
-        __builtin_nontemporal_store(w, reinterpret_cast<i4*>(wt + v));
+        if (FORM != 2) {
+            f4 s = __builtin_nontemporal_load(reinterpret_cast<f4*>(sdf + v));
+            s += 1.f;
+            __builtin_nontemporal_store(s, reinterpret_cast<f4*>(sdf + v));
+        }
+        if (FORM == 0) {
+            i4 w = __builtin_nontemporal_load(reinterpret_cast<i4*>(wt + v));
+            w += 1;
+            __builtin_nontemporal_store(w, reinterpret_cast<i4*>(wt + v));
+        } else {  // u16 weights in the same tiled layout: 2 B per voxel
+            h4* q = reinterpret_cast<h4*>(reinterpret_cast<unsigned short*>(wt) + v);
+            h4 w = __builtin_nontemporal_load(q);
+            w += (unsigned short)1;
+            __builtin_nontemporal_store(w, q);
+        }
     }
 }
 
@@ -68,8 +83,10 @@ int main() {
     for (unsigned uz = 4; uz < 12; ++uz)
         for (unsigned uy = 8; uy < 56; ++uy)
             for (unsigned x = 64; x < 448; ++x) box.push_back(pack(x, uy, uz));
-    const double bytes = (double)box.size() * 512.0 * 4.0;  // sdf + weight, read + write
+    for (int form = 0; form < 3; ++form)
     for (int order = 0; order < 3; ++order) {
+        // per unit of 128 voxels, read + write: sdf 512 B, weight 512 B (i32) or 256 B (u16)
+        const double bytes = (double)box.size() * 2.0 * (form == 0 ? 1024.0 : form == 1 ? 768.0 : 256.0);
         std::vector<unsigned> list = box;  // xrun: x fastest as built
         if (order == 1) std::sort(list.begin(), list.end(), [](unsigned a, unsigned b) { return unit_base(a) < unit_base(b); });
         if (order == 2) std::shuffle(list.begin(), list.end(), std::mt19937(1));
@@ -80,14 +97,15 @@ int main() {
             float best = 1e9f, ms;
             for (int r = 0; r < 6; ++r) {
                 CK(hipEventRecord(e0));
-                hipLaunchKernelGGL(k_rmw, dim3(grid), dim3(256), 0, 0, sdf, wt, dl, (unsigned)list.size());
+                auto k = form == 0 ? k_rmw<0> : form == 1 ? k_rmw<1> : k_rmw<2>;
+                hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, 0, sdf, wt, dl, (unsigned)list.size());
                 CK(hipEventRecord(e1));
                 CK(hipEventSynchronize(e1));
                 CK(hipEventElapsedTime(&ms, e0, e1));
                 best = std::min(best, ms);
             }
-            printf("order %-6s grid %4d: %zu units %.1f MB  %.1f us  %.0f GB/s\n",
-                   order == 0 ? "xrun" : order == 1 ? "zrun" : "random", grid, list.size(), bytes / 1e6, best * 1e3,
+            printf("form %-7s order %-6s grid %4d: %zu units %.1f MB  %.1f us  %.0f GB/s\n",
+                   form == 0 ? "i32" : form == 1 ? "u16" : "u16only", order == 0 ? "xrun" : order == 1 ? "zrun" : "random", grid, list.size(), bytes / 1e6, best * 1e3,
                    bytes / best / 1e6);
         }
         CK(hipFree(dl));
