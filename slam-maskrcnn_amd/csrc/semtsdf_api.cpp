@@ -22,6 +22,7 @@
 
 #include "../../include/semtsdf.h"
 #include "semtsdf_internal.h"
+#include "semtsdf_own.h"
 #include "semtsdf_wscan.h"
 
 using namespace semtsdf;
@@ -47,6 +48,20 @@ int fail(int code, const char* fmt, ...) {
             return fail(e_ == hipErrorOutOfMemory ? SEMTSDF_ERR_OOM : SEMTSDF_ERR_HIP, "%s: %s (%s:%d)", \
                         #expr, hipGetErrorString(e_), __FILE__, __LINE__);                          \
     } while (0)
+
+// The raw device allocator under the owners of semtsdf_own.h: out of memory has its own status, and
+// the error hipMalloc leaves behind is cleared (the handle stays usable).
+struct HipRaw {
+    static int alloc(void** p, size_t bytes) {
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e == hipSuccess) return SEMTSDF_OK;
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? SEMTSDF_ERR_OOM : SEMTSDF_ERR_HIP, "hipMalloc(%zu): %s", bytes,
+                    hipGetErrorString(e));
+    }
+    static void free(void* p) { (void)hipFree(p); }
+};
+using Scratch = CallScratch<HipRaw>;  // device scratch of one call
 
 // Palette of viewer.cu:93-126 (RGB triplets; written as BGR, viewer.cu:272).
 const uint8_t kPalette[kMaxObjects * 3] = {
@@ -75,7 +90,7 @@ struct semtsdf_vol {
     VolBufs b{};
     int device = 0;
     hipStream_t stream = nullptr;
-    size_t device_bytes = 0;
+    DevPool<HipRaw> pool;  // owns every device allocation of the handle (semtsdf_state::device_bytes)
     // per-frame staging (host-pointer API)
     uint16_t* depth_d = nullptr;
     uint8_t* rgb_d = nullptr;
@@ -170,27 +185,8 @@ size_t npx(const semtsdf_vol* v) { return (size_t)v->p.width * (size_t)v->p.heig
 
 hipStream_t pick(const semtsdf_vol* v, void* s) { return s ? (hipStream_t)s : v->stream; }
 
-int dev_alloc(semtsdf_vol* v, void** p, size_t bytes) {
-    if (bytes == 0) { *p = nullptr; return SEMTSDF_OK; }
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? SEMTSDF_ERR_OOM : SEMTSDF_ERR_HIP, "hipMalloc(%zu): %s", bytes,
-                    hipGetErrorString(e));
-    v->device_bytes += bytes;
-    return SEMTSDF_OK;
-}
-
 void free_all(semtsdf_vol* v) {
-    void* ptrs[] = {v->b.sdf, v->b.wt, v->b.bplain, v->b.boct, v->b.botmp, v->b.bdirty, v->b.dlist, v->b.sflag, v->b.color, v->b.hist, v->b.hmask, v->b.cls, v->b.cls_cnt, v->depth_d, v->rgb_d,
-                    v->mask_d, v->cls_d, v->tables_d, v->decision_d,
-                    v->num_objs_d, v->probs_d, v->box_d, v->palette_d, v->render_d, v->render_t_d, v->maps_d, v->track_d,
-                    v->counters_d, v->ray_state_d, v->rcp_table_d, v->wtrace_d, v->exact_d, v->px.bits, v->px.p, v->tile_cost_d, v->tile_perm_d, v->rare_d};
-    for (void* q : ptrs)
-        if (q) (void)hipFree(q);
-    for (auto& f : v->fs)
-        for (void* q : {(void*)f.pyr.px, (void*)f.pyr.l0, (void*)f.pyr.l1, (void*)f.unit_list, (void*)f.list_count,
-                        (void*)f.units})
-            if (q) (void)hipFree(q);
+    v->pool.release_all();
     if (v->decision_h) (void)hipHostFree(v->decision_h);
     for (auto* vec : {&v->ev_integrate, &v->ev_assoc, &v->ev_render, &v->ev_prep})
         for (auto& e : *vec) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -326,13 +322,12 @@ void screen_map(IntegrateArgs& a) {
 // A COLOR_I32 volume leaves byte colour storage for int32 x 4 (values converted on the device).
 int widen_color(semtsdf_vol* v, hipStream_t s) {
     if (v->color_wide) return SEMTSDF_OK;
-    void* wide = nullptr;
-    if (int rc = dev_alloc(v, &wide, v->g.nvox * 16)) return rc;
-    HIPC(launch_color_widen(static_cast<const uint8_t*>(v->b.color), static_cast<int32_t*>(wide), v->g.nvox, s));
-    HIPC(hipStreamSynchronize(s));
-    HIPC(hipFree(v->b.color));
-    v->device_bytes -= v->g.nvox * 4;
-    v->b.color = wide;
+    auto fill = [&](void* wide) {
+        HIPC(launch_color_widen(static_cast<const uint8_t*>(v->b.color), static_cast<int32_t*>(wide), v->g.nvox, s));
+        HIPC(hipStreamSynchronize(s));
+        return SEMTSDF_OK;
+    };
+    if (int rc = v->pool.swap(&v->b.color, v->g.nvox * 16, fill)) return rc;
     v->color_wide = true;
     return SEMTSDF_OK;
 }
@@ -340,13 +335,12 @@ int widen_color(semtsdf_vol* v, hipStream_t s) {
 // The weights leave uint16 storage for int32 (values converted on the device).
 int widen_weights(semtsdf_vol* v, hipStream_t s) {
     if (v->wt_wide) return SEMTSDF_OK;
-    void* wide = nullptr;
-    if (int rc = dev_alloc(v, &wide, v->g.nvox * 4)) return rc;
-    HIPC(launch_weight_widen(static_cast<const uint16_t*>(v->b.wt), static_cast<int32_t*>(wide), v->g.nvox, s));
-    HIPC(hipStreamSynchronize(s));
-    HIPC(hipFree(v->b.wt));
-    v->device_bytes -= v->g.nvox * 2;
-    v->b.wt = wide;
+    auto fill = [&](void* wide) {
+        HIPC(launch_weight_widen(static_cast<const uint16_t*>(v->b.wt), static_cast<int32_t*>(wide), v->g.nvox, s));
+        HIPC(hipStreamSynchronize(s));
+        return SEMTSDF_OK;
+    };
+    if (int rc = v->pool.swap(&v->b.wt, v->g.nvox * 4, fill)) return rc;
     v->wt_wide = true;
     v->b.wt_wide = 1;
     return SEMTSDF_OK;
@@ -498,7 +492,7 @@ int integrate_impl(semtsdf_vol* v, const uint16_t* depth_d, const uint8_t* rgb_d
     const bool wt = wt_path && wt_calls < 32;
     if (wt) {
         ++wt_calls;
-        if (!v->wtrace_d) HIPC(hipMalloc((void**)&v->wtrace_d, kWtSlots * kWaveTraceWords * 8));
+        if (int rc = v->wtrace_d ? 0 : v->pool.alloc((void**)&v->wtrace_d, kWtSlots * kWaveTraceWords * 8)) return rc;
         a.wtrace = v->wtrace_d;
         a.wtrace_slots = (unsigned)kWtSlots;
         HIPC(hipMemsetAsync(a.wtrace, 0, kWtSlots * kWaveTraceWords * 8, s));
@@ -652,12 +646,10 @@ int associate_impl(semtsdf_vol* v, uint8_t* mask_d, const float E[16], hipStream
         r.b = v->b;  // the map buffers as ensure_maps left them
         const int n = ((a.width + 15) / 16) * ((a.height + 15) / 16) + ((r.width + 15) / 16) * ((r.height + 15) / 16);
         if (n <= 8192 && n > v->tile_cap) {  // tile_order sorts up to 8192 tiles (256 x kTileOrderPer)
+            v->tile_n = 0;  // the new arrays start empty: nothing to carry over
             for (unsigned** q : {&v->tile_cost_d, &v->tile_perm_d})
-                if (*q) { (void)hipFree(*q); v->device_bytes -= (size_t)v->tile_cap * sizeof(unsigned); *q = nullptr; }
-            v->tile_cap = 0;
-            v->tile_n = 0;
-            if (int rc = dev_alloc(v, (void**)&v->tile_cost_d, (size_t)n * sizeof(unsigned))) return rc;
-            if (int rc = dev_alloc(v, (void**)&v->tile_perm_d, (size_t)n * sizeof(unsigned))) return rc;
+                if (int rc = v->pool.swap((void**)q, (size_t)n * sizeof(unsigned), [](void*) { return SEMTSDF_OK; }))
+                    return rc;  // one array may have grown: tile_cap, still the old count, fits both
             v->tile_cap = n;
         }
         if (n <= 8192) {
@@ -756,6 +748,30 @@ void tail_restore(T* a, int comps, int D, int d8, const std::vector<T>& buf) {
         std::copy(buf.begin() + k, buf.begin() + k + n * comps, a + off * comps);
         k += n * comps;
     });
+}
+
+// Voxels [vb, ve) of the reference layout (rows of lz planes, dense; host[0] is voxel vb, bpv bytes
+// per voxel) to or from the tiled device storage, in chunks of at most max_chunk voxels through a
+// device staging buffer of the host's layout: conv(stage, v0, nv) launches the layout conversion of
+// one chunk, after its copy in or before its copy out, and each chunk ends with a synchronise.
+template <class Conv>
+int staged_xfer(void* host, uint64_t vb, uint64_t ve, size_t bpv, uint64_t max_chunk, bool to_host, const char* what,
+                hipStream_t s, Conv&& conv) {
+    if (ve <= vb) return SEMTSDF_OK;
+    const uint64_t chunk = std::min<uint64_t>(ve - vb, max_chunk);
+    Scratch stage;
+    if (int rc = stage.alloc(chunk * bpv)) return rc;
+    for (uint64_t v0 = vb; v0 < ve; v0 += chunk) {
+        const uint64_t nv = std::min<uint64_t>(chunk, ve - v0);
+        void *h = static_cast<char*>(host) + (v0 - vb) * bpv, *d = stage.get();
+        const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice;
+        hipError_t e = to_host ? conv(d, v0, nv) : hipSuccess;  // out: convert, then copy
+        if (e == hipSuccess) e = hipMemcpyAsync(to_host ? h : d, to_host ? d : h, nv * bpv, kind, s);
+        if (e == hipSuccess && !to_host) e = conv(d, v0, nv);  // in: copy, then convert
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return fail(SEMTSDF_ERR_HIP, "%s transfer: %s", what, hipGetErrorString(e));
+    }
+    return SEMTSDF_OK;
 }
 }  // namespace
 
@@ -974,34 +990,23 @@ int semtsdf_create(const semtsdf_params* p, int device, semtsdf_vol** out) {
     if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) prio_greatest = 0;
     if (hipStreamCreateWithPriority(&v->stream, hipStreamNonBlocking, prio_greatest) != hipSuccess)
         return bail(fail(SEMTSDF_ERR_HIP, "hipStreamCreate failed"));
-    const bool ci32 = p->flags & SEMTSDF_F_COLOR_I32;
-    if ((rc = dev_alloc(v, (void**)&v->b.sdf, n * 4))) return bail(rc);
-    if ((rc = dev_alloc(v, &v->b.wt, n * 2))) return bail(rc);  // uint16 (wt_wide)
-    if ((rc = dev_alloc(v, (void**)&v->b.sflag, n / 32 + 1))) return bail(rc);
     const size_t nbricks = (size_t)g.nbx * g.nby * g.nbz;
-    if ((rc = dev_alloc(v, (void**)&v->b.bplain, nbricks * 4))) return bail(rc);
-    if ((rc = dev_alloc(v, (void**)&v->b.boct, nbricks * 8))) return bail(rc);
-    if ((rc = dev_alloc(v, (void**)&v->b.botmp, nbricks * 8))) return bail(rc);
     const size_t nquads = (size_t)g.nbx * g.nby * (size_t)((g.nbz + 3) / 4);
-    if ((rc = dev_alloc(v, (void**)&v->b.bdirty, nquads * 4))) return bail(rc);
-    if ((rc = dev_alloc(v, (void**)&v->b.dlist, (nquads + 1) * 4))) return bail(rc);
+    const size_t sem = (p->flags & SEMTSDF_F_SEMANTIC) ? 1 : 0, vote = (p->flags & SEMTSDF_F_VOTE) ? 1 : 0;
+    // The volume, then the frame staging of the host-pointer API, in this order.  An array the mode does not
+    // have is of zero bytes: a null pointer.  Weights start as uint16 (wt_wide), and the colours of a
+    // COLOR_I32 volume as bytes (color_wide).
+    rc = v->pool.alloc_group({{(void**)&v->b.sdf, n * 4}, {&v->b.wt, n * 2}, {(void**)&v->b.sflag, n / 32 + 1},
+                              {(void**)&v->b.bplain, nbricks * 4}, {(void**)&v->b.boct, nbricks * 8},
+                              {(void**)&v->b.botmp, nbricks * 8}, {(void**)&v->b.bdirty, nquads * 4},
+                              {(void**)&v->b.dlist, (nquads + 1) * 4}, {&v->b.color, n * 4},
+                              {(void**)&v->b.hist, sem * n * kMaxObjects * 4}, {(void**)&v->b.hmask, sem * n * 4},
+                              {(void**)&v->b.cls, vote * n * 4}, {(void**)&v->b.cls_cnt, vote * n * 4},
+                              {(void**)&v->cls_d, vote * px * 4}, {(void**)&v->depth_d, px * 2},
+                              {(void**)&v->rgb_d, px * 3}, {(void**)&v->mask_d, px}});
+    if (rc) return bail(rc);
     if (nquads && (hipMemset(v->b.bdirty, 0, nquads * 4) != hipSuccess || hipMemset(v->b.dlist, 0, 4) != hipSuccess))
         return bail(fail(SEMTSDF_ERR_HIP, "memset failed"));
-    (void)ci32;  // COLOR_I32 volumes start with byte storage (color_wide)
-    if ((rc = dev_alloc(v, &v->b.color, g.nvox * 4))) return bail(rc);
-    if (p->flags & SEMTSDF_F_SEMANTIC)
-    {
-        if ((rc = dev_alloc(v, (void**)&v->b.hist, g.nvox * kMaxObjects * 4))) return bail(rc);
-        if ((rc = dev_alloc(v, (void**)&v->b.hmask, n * 4))) return bail(rc);
-    }
-    if (p->flags & SEMTSDF_F_VOTE) {
-        if ((rc = dev_alloc(v, (void**)&v->b.cls, n * 4))) return bail(rc);
-        if ((rc = dev_alloc(v, (void**)&v->b.cls_cnt, n * 4))) return bail(rc);
-        if ((rc = dev_alloc(v, (void**)&v->cls_d, px * 4))) return bail(rc);
-    }
-    if ((rc = dev_alloc(v, (void**)&v->depth_d, px * 2))) return bail(rc);
-    if ((rc = dev_alloc(v, (void**)&v->rgb_d, px * 3))) return bail(rc);
-    if ((rc = dev_alloc(v, (void**)&v->mask_d, px))) return bail(rc);
     for (auto& f : v->fs) {
         DepthPyramid& pyr = f.pyr;
         pyr.w0 = (p->width + 7) / 8; pyr.h0 = (p->height + 7) / 8;
@@ -1009,43 +1014,40 @@ int semtsdf_create(const semtsdf_params* p, int device, semtsdf_vol** out) {
         pyr.rs = 4u * (unsigned)((p->width + 1 + 3) / 4 * 4);
         // the zero column u = W and row v = H (and the padding of the last band) stay zero
         const size_t nrec = (size_t)pyr.rs * (size_t)((p->height + 1 + 3) / 4);
-        if ((rc = dev_alloc(v, (void**)&pyr.px, nrec * 8))) return bail(rc);
+        if ((rc = v->pool.alloc((void**)&pyr.px, nrec * 8))) return bail(rc);
         if (hipMemset(pyr.px, 0, nrec * 8) != hipSuccess) return bail(fail(SEMTSDF_ERR_HIP, "memset failed"));
-        if ((rc = dev_alloc(v, (void**)&pyr.l0, (size_t)pyr.w1 * 4 * pyr.h1 * 4 * sizeof(uint2)))) return bail(rc);
-        if ((rc = dev_alloc(v, (void**)&pyr.l1, (size_t)pyr.w1 * pyr.h1 * sizeof(uint2)))) return bail(rc);
-        if ((rc = dev_alloc(v, (void**)&f.unit_list, unit_list_capacity(g) * sizeof(unsigned)))) return bail(rc);
-        if ((rc = dev_alloc(v, (void**)&f.list_count, kListCountWords * sizeof(unsigned)))) return bail(rc);
+        if ((rc = v->pool.alloc((void**)&pyr.l0, (size_t)pyr.w1 * 4 * pyr.h1 * 4 * sizeof(uint2)))) return bail(rc);
+        if ((rc = v->pool.alloc((void**)&pyr.l1, (size_t)pyr.w1 * pyr.h1 * sizeof(uint2)))) return bail(rc);
+        if ((rc = v->pool.alloc((void**)&f.unit_list, unit_list_capacity(g) * sizeof(unsigned)))) return bail(rc);
+        if ((rc = v->pool.alloc((void**)&f.list_count, kListCountWords * sizeof(unsigned)))) return bail(rc);
         // every unit in at most one list, + one pad per list, bases rounded up to even; at least two
         // entries per persistent wave (k_integrate reads a wave's first free group unconditionally)
         const uint64_t nunits = std::max<uint64_t>(unit_count(g) + 2 * kLists + 2, 2u * (uint64_t)kPreWaves + 6u);
         // + the first-group table of the XCD split (two entries per wave slot, k_compact_lists)
-        if ((rc = dev_alloc(v, (void**)&f.units, (nunits + 2u * (uint64_t)kPreWaves) * sizeof(unsigned)))) return bail(rc);
+        if ((rc = v->pool.alloc((void**)&f.units, (nunits + 2u * (uint64_t)kPreWaves) * sizeof(unsigned)))) return bail(rc);
         f.first_tab = f.units + nunits;
     }
-    if ((rc = dev_alloc(v, (void**)&v->rcp_table_d, kRcpTable * sizeof(float)))) return bail(rc);
+    // the association's per-pixel data: an unsharded SEMANTIC volume's only
+    const size_t apx = (sem && p->z_nshards == 1) ? px : 0;
+    rc = v->pool.alloc_group({{(void**)&v->rcp_table_d, kRcpTable * sizeof(float)},
+                              {(void**)&v->tables_d, sizeof(AssocTables)}, {(void**)&v->decision_d, sizeof(*v->decision_d)},
+                              {(void**)&v->exact_d, sizeof(AssocExact)}, {(void**)&v->px.bits, apx * sizeof(uint2)},
+                              {(void**)&v->px.p, apx * kMaxObjects * sizeof(float)}, {(void**)&v->num_objs_d, 16},
+                              {(void**)&v->counters_d, kCounters * sizeof(unsigned long long)},
+                              {(void**)&v->rare_d, sizeof(IntegrateRare)}, {(void**)&v->palette_d, sizeof(kPalette)}});
+    if (rc) return bail(rc);
     {
         float t[kRcpTable];
         for (int i = 0; i < kRcpTable; ++i) t[i] = 1.0f / (float)(i + 1);  // IEEE: correctly rounded
         if (hipMemcpy(v->rcp_table_d, t, sizeof(t), hipMemcpyHostToDevice) != hipSuccess)
             return bail(fail(SEMTSDF_ERR_HIP, "rcp table upload failed"));
     }
-    if ((rc = dev_alloc(v, (void**)&v->tables_d, sizeof(AssocTables)))) return bail(rc);
-    if ((rc = dev_alloc(v, (void**)&v->decision_d, sizeof(AssocDecision)))) return bail(rc);
-    if ((rc = dev_alloc(v, (void**)&v->exact_d, sizeof(AssocExact)))) return bail(rc);
     if (hipMemset(v->exact_d, 0, sizeof(AssocExact)) != hipSuccess) return bail(fail(SEMTSDF_ERR_HIP, "memset failed"));
-    if ((p->flags & SEMTSDF_F_SEMANTIC) && p->z_nshards == 1) {  // the association's per-pixel data
-        if ((rc = dev_alloc(v, (void**)&v->px.bits, npx(v) * sizeof(uint2)))) return bail(rc);
-        if ((rc = dev_alloc(v, (void**)&v->px.p, npx(v) * kMaxObjects * sizeof(float)))) return bail(rc);
-    }
-    if ((rc = dev_alloc(v, (void**)&v->num_objs_d, 16))) return bail(rc);
-    if ((rc = dev_alloc(v, (void**)&v->counters_d, kCounters * sizeof(unsigned long long)))) return bail(rc);
-    if ((rc = dev_alloc(v, (void**)&v->rare_d, sizeof(IntegrateRare)))) return bail(rc);
     {
         const IntegrateRare r{v->b.bdirty, v->b.dlist, g.nby, g.nbz, v->counters_d};
         if (hipMemcpy(v->rare_d, &r, sizeof(r), hipMemcpyHostToDevice) != hipSuccess)
             return bail(fail(SEMTSDF_ERR_HIP, "upload of the integrate's rare-path fields failed"));
     }
-    if ((rc = dev_alloc(v, (void**)&v->palette_d, sizeof(kPalette)))) return bail(rc);
     if (hipHostMalloc((void**)&v->decision_h, sizeof(AssocDecision), 0) != hipSuccess)
         return bail(fail(SEMTSDF_ERR_HIP, "hipHostMalloc failed"));
     if (hipMemcpy(v->palette_d, kPalette, sizeof(kPalette), hipMemcpyHostToDevice) != hipSuccess)
@@ -1084,7 +1086,7 @@ int semtsdf_get_state(const semtsdf_vol* v, semtsdf_state* out) {
     out->local_dim[1] = v->g.dimy;
     out->local_dim[2] = v->g.lz;
     out->local_voxels = (uint64_t)v->g.dimx * v->g.dimy * v->g.lz;
-    out->device_bytes = v->device_bytes;
+    out->device_bytes = v->pool.bytes();
     out->label_votes_dropped = dropped;
     return SEMTSDF_OK;
 }
@@ -1107,12 +1109,9 @@ int semtsdf_reset(semtsdf_vol* v, void* stream) {
     if (int rc = after_maps(v, s)) return rc;
     HIPC(launch_fill_volume(v->g, v->b, v->p.flags, s));
     if (v->wt_wide) {  // all weights are 0 again: back to uint16 storage
-        void* narrow = nullptr;
-        if (int rc = dev_alloc(v, &narrow, n * 2)) return rc;
-        HIPC(hipStreamSynchronize(s));
-        HIPC(hipFree(v->b.wt));
-        v->device_bytes -= n * 4;
-        v->b.wt = narrow;
+        // (the fill and what was queued before it are done with the wide array once s is idle)
+        if (int rc = v->pool.swap(&v->b.wt, n * 2, [&](void*) { HIPC(hipStreamSynchronize(s)); return SEMTSDF_OK; }))
+            return rc;
         v->wt_wide = false;
         v->b.wt_wide = 0;
     }
@@ -1285,12 +1284,8 @@ int semtsdf_assoc_probs(semtsdf_vol* v, const float E[16], float* probs, uint8_t
     HIPC(hipSetDevice(v->device));
     hipStream_t s = pick(v, stream);
     const size_t n = npx(v) * kMaxObjects;
-    if (!v->probs_d) {
-        int rc = dev_alloc(v, (void**)&v->probs_d, n * 4);
-        if (rc) return rc;
-        rc = dev_alloc(v, (void**)&v->box_d, n);
-        if (rc) return rc;
-    }
+    if (!v->probs_d)
+        if (int rc = v->pool.alloc_group({{(void**)&v->probs_d, n * 4}, {(void**)&v->box_d, n}})) return rc;
     // tables scratch is reused; the mask is all-zero so no log terms are needed
     HIPC(hipMemsetAsync(v->mask_d, 0, npx(v), s));
     HIPC(hipMemsetAsync(v->tables_d, 0, sizeof(AssocTables), s));
@@ -1485,10 +1480,7 @@ int semtsdf_shard_ray_begin(semtsdf_vol* v, int kind, const float cam[16], const
     if (kind == SEMTSDF_RAY_ASSOC && v->n_obs == 0)
         return fail(SEMTSDF_ERR_STATE, "association needs n_obs > 0 (tsdf.cu:426)");
     HIPC(hipSetDevice(v->device));
-    if (!v->ray_state_d) {
-        int rc = dev_alloc(v, &v->ray_state_d, 24 * npx(v));
-        if (rc) return rc;
-    }
+    if (int rc = v->ray_state_d ? 0 : v->pool.alloc(&v->ray_state_d, 24 * npx(v))) return rc;
     if (kind == SEMTSDF_RAY_ASSOC) {
         v->ray_cam = assoc_camera(v, cam);
     } else {
@@ -1710,19 +1702,19 @@ int semtsdf_copy_bandwidth(int device, size_t bytes, int reps, double* gbs) {
     if (!gbs || bytes < 16 || reps < 1) return fail(SEMTSDF_ERR_INVALID, "bad argument");
     HIPC(hipSetDevice(device));
     bytes &= ~(size_t)15;
-    void *a = nullptr, *b = nullptr;
+    Scratch a, b;
     hipStream_t s = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc = SEMTSDF_OK;
     float best = 1e30f;
-    if (hipMalloc(&a, bytes) != hipSuccess || hipMalloc(&b, bytes) != hipSuccess ||
+    if (a.alloc(bytes) || b.alloc(bytes) ||
         hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&e0) != hipSuccess ||
-        hipEventCreate(&e1) != hipSuccess || hipMemsetAsync(a, 0, bytes, s) != hipSuccess) {
+        hipEventCreate(&e1) != hipSuccess || hipMemsetAsync(a.get(), 0, bytes, s) != hipSuccess) {
         rc = fail(SEMTSDF_ERR_HIP, "copy_bandwidth setup failed");
     } else {
         for (int r = 0; r <= reps && rc == SEMTSDF_OK; ++r) {
             float ms = 0.0f;
-            if (hipEventRecord(e0, s) != hipSuccess || launch_copy_f4(a, b, bytes / 16, s) != hipSuccess ||
+            if (hipEventRecord(e0, s) != hipSuccess || launch_copy_f4(a.get(), b.get(), bytes / 16, s) != hipSuccess ||
                 hipEventRecord(e1, s) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
                 hipEventElapsedTime(&ms, e0, e1) != hipSuccess)
                 rc = fail(SEMTSDF_ERR_HIP, "copy_bandwidth run failed");
@@ -1734,8 +1726,6 @@ int semtsdf_copy_bandwidth(int device, size_t bytes, int reps, double* gbs) {
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (s) (void)hipStreamDestroy(s);
-    if (a) (void)hipFree(a);
-    if (b) (void)hipFree(b);
     return rc;
 }
 
@@ -1790,7 +1780,9 @@ static int raycast_impl(semtsdf_vol* v, const float s2w[16], const float c[3], i
     // per-wave timestamps of every render
     static const char* rs_path = getenv("SEMTSDF_RAY_STATS");
     const size_t rs_words = npx(v) * 4 + ((npx(v) + 63) / 64 + 64) * 4;
-    if (rs_path) HIPC(hipMalloc((void**)&a.ray_stats, rs_words * 4));
+    Scratch rs;  // stays empty unless the instrumentation is on
+    if (int rc = rs_path ? rs.alloc(rs_words * 4) : 0) return rc;
+    a.ray_stats = rs.get<unsigned>();
     if (rs_path) HIPC(hipMemsetAsync(a.ray_stats, 0, rs_words * 4, s));
     static const char* rows = getenv("SEMTSDF_RENDER_ROWS");  // instrumentation: "r0,r1"
     if (rows && sscanf(rows, "%d,%d", &a.row0, &a.row1) != 2) a.row0 = a.row1 = 0;
@@ -1801,7 +1793,6 @@ static int raycast_impl(semtsdf_vol* v, const float s2w[16], const float c[3], i
         std::vector<unsigned> h(rs_words);
         HIPC(hipMemcpyAsync(h.data(), a.ray_stats, rs_words * 4, hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
-        HIPC(hipFree(a.ray_stats));
         if (FILE* f = fopen(rs_path, "ab")) {
             fwrite(h.data(), 4, h.size(), f);
             fclose(f);
@@ -1826,12 +1817,8 @@ int semtsdf_raycast(semtsdf_vol* v, const float s2w[16], const float c[3], int m
     HIPC(hipSetDevice(v->device));
     hipStream_t s = pick(v, stream);
     const size_t n = npx(v);
-    if (!v->render_d) {
-        int rc = dev_alloc(v, (void**)&v->render_d, n * 3);
-        if (rc) return rc;
-        rc = dev_alloc(v, (void**)&v->render_t_d, n * 4);
-        if (rc) return rc;
-    }
+    if (!v->render_d)
+        if (int rc = v->pool.alloc_group({{(void**)&v->render_d, n * 3}, {(void**)&v->render_t_d, n * 4}})) return rc;
     int rc = raycast_impl(v, s2w, c, mode, v->render_d, v->render_t_d, s);
     if (rc) return rc;
     HIPC(hipMemcpyAsync(out_bgr, v->render_d, n * 3, hipMemcpyDeviceToHost, s));
@@ -1914,12 +1901,8 @@ int semtsdf_render_maps(semtsdf_vol* v, const float s2w[16], const float c[3], i
     HIPC(hipSetDevice(v->device));
     hipStream_t s = pick(v, stream);
     const size_t n = npx(v);
-    if (!v->maps_d) {  // t, point, normal, votes (4-B aligned), then label and flags
-        if (int rc = dev_alloc(v, (void**)&v->maps_d, n * 34)) {
-            v->maps_d = nullptr;
-            return rc;
-        }
-    }
+    // t, point, normal, votes (4-B aligned), then label and flags
+    if (int rc = v->maps_d ? 0 : v->pool.alloc((void**)&v->maps_d, n * 34)) return rc;
     float* f = reinterpret_cast<float*>(v->maps_d);
     semtsdf_maps_out d{};
     d.t = out_host->t ? f : nullptr;
@@ -1943,12 +1926,7 @@ int semtsdf_render_maps(semtsdf_vol* v, const float s2w[16], const float c[3], i
 // Device scratch of the host-pointer variants, 52 B per pixel + the words: the 4-B aligned arrays
 // first (frame vertex, normal; model point, normal; the words), then the two flag maps and the depth.
 static int track_scratch(semtsdf_vol* v) {
-    if (v->track_d) return SEMTSDF_OK;
-    if (int rc = dev_alloc(v, (void**)&v->track_d, npx(v) * 52 + kIcpWords * 8)) {
-        v->track_d = nullptr;
-        return rc;
-    }
-    return SEMTSDF_OK;
+    return v->track_d ? SEMTSDF_OK : v->pool.alloc((void**)&v->track_d, npx(v) * 52 + kIcpWords * 8);
 }
 
 static int frame_maps_check(semtsdf_vol* v, const uint16_t* depth, float* vertex, float* normal, uint8_t* flags) {
@@ -2078,67 +2056,36 @@ int semtsdf_icp_system(semtsdf_vol* v, const semtsdf_icp_in* in_host, const floa
     return SEMTSDF_OK;
 }
 
-// A 4-byte per-voxel array between the reference layout (rows of lz planes, dense) and the
-// tiled device storage, chunked through a device staging buffer.
 // Voxels of the reference layout (rows of lz planes) held by the handle.
 static uint64_t nref(const semtsdf_vol* v) { return (uint64_t)v->g.dimx * v->g.dimy * v->g.lz; }
 
-// Voxels [vb, ve) of the reference layout (host[0] is voxel vb).
+// A 4-byte per-voxel array, <= 256 MiB staging.
 // dev_u16: the device array holds uint16_t (narrow weights), the host side int32 all the same.
 static int vox_xfer(semtsdf_vol* v, void* host, void* dev, bool to_host, const char* what, hipStream_t s, uint64_t vb,
                     uint64_t ve, bool dev_u16 = false) {
-    if (ve <= vb) return SEMTSDF_OK;
-    const uint64_t chunk = std::min<uint64_t>(ve - vb, 1ull << 26);  // <= 256 MiB staging
-    void* stage = nullptr;
-    HIPC(hipMalloc(&stage, chunk * 4));
-    for (uint64_t v0 = vb; v0 < ve; v0 += chunk) {
-        const uint64_t nv = std::min<uint64_t>(chunk, ve - v0);
-        char* h = static_cast<char*>(host) + (v0 - vb) * 4;
-        hipError_t e;
-        if (to_host) {
-            e = launch_vox_chunk(dev, stage, true, v->g, v0, nv, s, dev_u16);
-            if (e == hipSuccess) e = hipMemcpyAsync(h, stage, nv * 4, hipMemcpyDeviceToHost, s);
-        } else {
-            e = hipMemcpyAsync(stage, h, nv * 4, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = launch_vox_chunk(stage, dev, false, v->g, v0, nv, s, dev_u16);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            (void)hipFree(stage);
-            return fail(SEMTSDF_ERR_HIP, "%s transfer: %s", what, hipGetErrorString(e));
-        }
-    }
-    HIPC(hipFree(stage));
-    return SEMTSDF_OK;
+    auto conv = [&](void* stage, uint64_t v0, uint64_t nv) {
+        return launch_vox_chunk(to_host ? dev : stage, to_host ? stage : dev, to_host, v->g, v0, nv, s, dev_u16);
+    };
+    return staged_xfer(host, vb, ve, 4, 1ull << 26, to_host, what, s, conv);
 }
 
 // colour between the padded device layout and the reference [N][3] layout, chunked
 static int color_xfer(semtsdf_vol* v, void* host, bool to_host, hipStream_t s, uint64_t vb, uint64_t ve) {
     const bool i32 = v->p.flags & SEMTSDF_F_COLOR_I32;  // the boundary's element type
-    const size_t es = i32 ? 4 : 1;
-    if (ve <= vb) return SEMTSDF_OK;
-    const uint64_t chunk = std::min<uint64_t>(ve - vb, 1ull << 24);
-    void* stage = nullptr;
-    HIPC(hipMalloc(&stage, chunk * 3 * es));
-    for (uint64_t v0 = vb; v0 < ve; v0 += chunk) {
-        const uint64_t nv = std::min<uint64_t>(chunk, ve - v0);
-        char* h = static_cast<char*>(host) + (v0 - vb) * 3 * es;
-        hipError_t e;
-        if (to_host) {
-            e = launch_color_chunk(v->b.color, stage, true, i32, v->color_wide, v->g, v0, nv, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(h, stage, nv * 3 * es, hipMemcpyDeviceToHost, s);
-        } else {
-            e = hipMemcpyAsync(stage, h, nv * 3 * es, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = launch_color_chunk(stage, v->b.color, false, i32, v->color_wide, v->g, v0, nv, s);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            (void)hipFree(stage);
-            return fail(SEMTSDF_ERR_HIP, "colour transfer: %s", hipGetErrorString(e));
-        }
-    }
-    HIPC(hipFree(stage));
-    return SEMTSDF_OK;
+    auto conv = [&](void* stage, uint64_t v0, uint64_t nv) {
+        return to_host ? launch_color_chunk(v->b.color, stage, true, i32, v->color_wide, v->g, v0, nv, s)
+                       : launch_color_chunk(stage, v->b.color, false, i32, v->color_wide, v->g, v0, nv, s);
+    };
+    return staged_xfer(host, vb, ve, i32 ? 12 : 3, 1ull << 24, to_host, "colour", s, conv);
+}
+
+// the histogram between the device's layout and the reference [N][32] layout, <= 512 MiB staging
+static int hist_xfer(semtsdf_vol* v, uint32_t* host, bool to_host, hipStream_t s, uint64_t vb, uint64_t ve) {
+    auto conv = [&](void* stage, uint64_t v0, uint64_t nv) {
+        return to_host ? launch_hist_chunk_to_vm(v->b.hist, static_cast<uint32_t*>(stage), v->g, v0, nv, s)
+                       : launch_hist_chunk_to_bm(static_cast<uint32_t*>(stage), v->b.hist, v->g, v0, nv, s);
+    };
+    return staged_xfer(host, vb, ve, kMaxObjects * 4, 1ull << 22, to_host, "histogram", s, conv);
 }
 
 int semtsdf_download_slab(semtsdf_vol* v, int x0, int x1, float* sdf, int32_t* wt, void* color, uint32_t* hist,
@@ -2152,10 +2099,7 @@ int semtsdf_download_slab(semtsdf_vol* v, int x0, int x1, float* sdf, int32_t* w
     int rc;
     if (sdf && (rc = vox_xfer(v, sdf, v->b.sdf, true, "sdf", s, vb, ve))) return rc;
     if (wt && (rc = vox_xfer(v, wt, v->b.wt, true, "weight", s, vb, ve, !v->wt_wide))) return rc;
-    if (color) {
-        rc = color_xfer(v, color, true, s, vb, ve);
-        if (rc) return rc;
-    }
+    if (color && (rc = color_xfer(v, color, true, s, vb, ve))) return rc;
     if (cls) {
         if (!(v->p.flags & SEMTSDF_F_VOTE)) return fail(SEMTSDF_ERR_STATE, "not a VOTE volume");
         if ((rc = vox_xfer(v, cls, v->b.cls, true, "cls", s, vb, ve))) return rc;
@@ -2166,21 +2110,7 @@ int semtsdf_download_slab(semtsdf_vol* v, int x0, int x1, float* sdf, int32_t* w
     }
     if (hist) {
         if (!(v->p.flags & SEMTSDF_F_SEMANTIC)) return fail(SEMTSDF_ERR_STATE, "not a SEMANTIC volume");
-        const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(ve - vb, 1ull << 22));  // <= 512 MiB staging
-        uint32_t* stage = nullptr;
-        HIPC(hipMalloc(&stage, chunk * kMaxObjects * 4));
-        for (uint64_t v0 = vb; v0 < ve; v0 += chunk) {
-            const uint64_t nv = std::min<uint64_t>(chunk, ve - v0);
-            hipError_t e = launch_hist_chunk_to_vm(v->b.hist, stage, v->g, v0, nv, s);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(hist + (v0 - vb) * kMaxObjects, stage, nv * kMaxObjects * 4, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) {
-                (void)hipFree(stage);
-                return fail(SEMTSDF_ERR_HIP, "histogram download: %s", hipGetErrorString(e));
-            }
-        }
-        HIPC(hipFree(stage));
+        if ((rc = hist_xfer(v, hist, true, s, vb, ve))) return rc;
     }
     HIPC(hipStreamSynchronize(s));
     return SEMTSDF_OK;
@@ -2208,8 +2138,7 @@ int semtsdf_upload(semtsdf_vol* v, const float* sdf, const int32_t* wt, const vo
         // one pass over the values: their upper bound, and whether uint16 storage holds them all
         const WeightScan ws = scan_weights(wt, nref(v));
         if (!ws.fits_u16 && (rc = widen_weights(v, s))) return rc;
-        rc = vox_xfer(v, const_cast<int32_t*>(wt), v->b.wt, false, "weight", s, 0, nref(v), !v->wt_wide);
-        if (rc) return rc;
+        if ((rc = vox_xfer(v, const_cast<int32_t*>(wt), v->b.wt, false, "weight", s, 0, nref(v), !v->wt_wide))) return rc;
         v->wmax_bound = ws.wmax;
     }
     if (color) {
@@ -2221,8 +2150,7 @@ int semtsdf_upload(semtsdf_vol* v, const float* sdf, const int32_t* wt, const vo
             for (uint64_t i = 0; i < nc && fits; ++i) fits = (uint32_t)c[i] <= 255u;
             if (!fits && (rc = widen_color(v, s))) return rc;
         }
-        rc = color_xfer(v, const_cast<void*>(color), false, s, 0, nref(v));
-        if (rc) return rc;
+        if ((rc = color_xfer(v, const_cast<void*>(color), false, s, 0, nref(v)))) return rc;
     }
     if (cls) {
         if (!(v->p.flags & SEMTSDF_F_VOTE)) return fail(SEMTSDF_ERR_STATE, "not a VOTE volume");
@@ -2236,22 +2164,7 @@ int semtsdf_upload(semtsdf_vol* v, const float* sdf, const int32_t* wt, const vo
         if (!(v->p.flags & SEMTSDF_F_SEMANTIC)) return fail(SEMTSDF_ERR_STATE, "not a SEMANTIC volume");
         // bin mask "every bin may be present" until it is rebuilt from the new histogram
         HIPC(hipMemsetAsync(v->b.hmask, 0xFF, v->g.nvox * 4, s));
-        const uint64_t n = (uint64_t)v->g.dimx * v->g.dimy * v->g.lz;
-        const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, 1ull << 22));
-        uint32_t* stage = nullptr;
-        HIPC(hipMalloc(&stage, chunk * kMaxObjects * 4));
-        for (uint64_t v0 = 0; v0 < n; v0 += chunk) {
-            const uint64_t nv = std::min<uint64_t>(chunk, n - v0);
-            hipError_t e =
-                hipMemcpyAsync(stage, hist + v0 * kMaxObjects, nv * kMaxObjects * 4, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = launch_hist_chunk_to_bm(stage, v->b.hist, v->g, v0, nv, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) {
-                (void)hipFree(stage);
-                return fail(SEMTSDF_ERR_HIP, "histogram upload: %s", hipGetErrorString(e));
-            }
-        }
-        HIPC(hipFree(stage));
+        if ((rc = hist_xfer(v, const_cast<uint32_t*>(hist), false, s, 0, nref(v)))) return rc;
         HIPC(launch_hist_mask(v->g, v->b, s));
     }
     v->maps_stale = true;
@@ -2279,13 +2192,9 @@ int semtsdf_export_surface(semtsdf_vol* v, float sdf_max, int32_t min_weight, se
     HIPC(hipSetDevice(v->device));
     hipStream_t s = v->stream;
     if (int rc = after_maps(v, s)) return rc;
-    unsigned long long* cnt_d = nullptr;
-    HIPC(hipMalloc((void**)&cnt_d, sizeof(unsigned long long)));
-    SurfacePoint* pts_d = nullptr;
-    auto cleanup = [&]() {
-        if (cnt_d) (void)hipFree(cnt_d);
-        if (pts_d) (void)hipFree(pts_d);
-    };
+    Scratch cnt, pts;
+    if (int rc = cnt.alloc(sizeof(unsigned long long))) return rc;
+    unsigned long long* cnt_d = cnt.get<unsigned long long>();
     auto run = [&](SurfacePoint* o, uint64_t cap, unsigned long long* n) -> hipError_t {
         hipError_t e = hipMemsetAsync(cnt_d, 0, sizeof(unsigned long long), s);
         if (e == hipSuccess) e = launch_export_surface(v->g, v->b, sdf_max, min_weight, v->color_wide ? 1 : 0,
@@ -2296,16 +2205,14 @@ int semtsdf_export_surface(semtsdf_vol* v, float sdf_max, int32_t min_weight, se
     };
     unsigned long long n = 0;
     hipError_t e = run(nullptr, 0, &n);
-    if (e != hipSuccess) { cleanup(); return fail(SEMTSDF_ERR_HIP, "surface count: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(SEMTSDF_ERR_HIP, "surface count: %s", hipGetErrorString(e));
     *count = n;
-    if (!out || n == 0 || capacity == 0) { cleanup(); return SEMTSDF_OK; }
-    e = hipMalloc((void**)&pts_d, n * sizeof(SurfacePoint));
-    if (e != hipSuccess) { cleanup(); return fail(SEMTSDF_ERR_OOM, "surface export: %s", hipGetErrorString(e)); }
+    if (!out || n == 0 || capacity == 0) return SEMTSDF_OK;
+    if (pts.alloc(n * sizeof(SurfacePoint))) return fail(SEMTSDF_ERR_OOM, "surface export: no memory for %llu points", n);
     unsigned long long n2 = 0;
-    e = run(pts_d, n, &n2);
+    e = run(pts.get<SurfacePoint>(), n, &n2);
     std::vector<SurfacePoint> h(n);
-    if (e == hipSuccess) e = hipMemcpy(h.data(), pts_d, n * sizeof(SurfacePoint), hipMemcpyDeviceToHost);
-    cleanup();
+    if (e == hipSuccess) e = hipMemcpy(h.data(), pts.get(), n * sizeof(SurfacePoint), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(SEMTSDF_ERR_HIP, "surface export: %s", hipGetErrorString(e));
     if (n2 != n) return fail(SEMTSDF_ERR_STATE, "surface export: count changed (%llu, %llu)", n, n2);
     // the reference's flat order (x-major, z fastest)
@@ -2329,21 +2236,7 @@ int semtsdf_extract_mesh(semtsdf_vol* v, int32_t min_weight, semtsdf_mesh_vertex
     const uint64_t nb = mesh_blocks(v->g);
     // scratch of the call, one allocation per pass: 29 B per 256-voxel tile to count; 4 B per stored
     // voxel and the outputs to emit
-    char* count_d = nullptr;
-    char* emit_d = nullptr;
-    auto done = [&](int rc) {
-        if (count_d) (void)hipFree(count_d);
-        if (emit_d) (void)hipFree(emit_d);
-        return rc;
-    };
-    auto alloc = [&](char** p, uint64_t bytes) {
-        const hipError_t e = hipMalloc((void**)p, bytes);
-        if (e == hipSuccess) return SEMTSDF_OK;
-        *p = nullptr;
-        (void)hipGetLastError();  // the handle stays usable
-        return fail(e == hipErrorOutOfMemory ? SEMTSDF_ERR_OOM : SEMTSDF_ERR_HIP, "mesh scratch hipMalloc(%llu): %s",
-                    (unsigned long long)bytes, hipGetErrorString(e));
-    };
+    Scratch count_s, emit_s;
     uint64_t off = 0;
     auto carve = [&](uint64_t bytes) {  // 256-B aligned parts of one allocation
         const uint64_t at = off;
@@ -2353,7 +2246,8 @@ int semtsdf_extract_mesh(semtsdf_vol* v, int32_t min_weight, semtsdf_mesh_vertex
     const uint64_t o_tot = carve(2 * sizeof(unsigned long long)), o_cnt = carve(nb * sizeof(uint2)),
                    o_gsum = carve(mesh_groups(v->g) * 2 * sizeof(unsigned long long)),
                    o_list = carve(mesh_list_words(v->g) * sizeof(uint32_t)), o_base = carve(nb * sizeof(ulonglong2));
-    if (int rc = alloc(&count_d, off)) return done(rc);
+    if (int rc = count_s.alloc(off)) return rc;
+    char* count_d = count_s.get<char>();
     unsigned long long* tot_d = (unsigned long long*)(count_d + o_tot);
     uint2* cnt_d = (uint2*)(count_d + o_cnt);
     unsigned long long* gsum_d = (unsigned long long*)(count_d + o_gsum);
@@ -2365,20 +2259,21 @@ int semtsdf_extract_mesh(semtsdf_vol* v, int32_t min_weight, semtsdf_mesh_vertex
     if (e == hipSuccess) e = hipMemcpyAsync(tot, tot_d, sizeof(tot), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(listed, alist_d, sizeof(listed), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return done(fail(SEMTSDF_ERR_HIP, "mesh count: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(SEMTSDF_ERR_HIP, "mesh count: %s", hipGetErrorString(e));
     *nverts = tot[0];
     *ntris = tot[1];
     if (tot[0] >= (1ull << 32))
-        return done(fail(SEMTSDF_ERR_UNSUPPORTED, "mesh of %llu vertices: indices are 32-bit", tot[0]));
-    if (!verts) return done(SEMTSDF_OK);
+        return fail(SEMTSDF_ERR_UNSUPPORTED, "mesh of %llu vertices: indices are 32-bit", tot[0]);
+    if (!verts) return SEMTSDF_OK;
     if (vcap < tot[0] || tcap < tot[1])
-        return done(fail(SEMTSDF_ERR_INVALID, "mesh of %llu vertices and %llu triangles exceeds the capacities %llu, %llu",
-                         tot[0], tot[1], (unsigned long long)vcap, (unsigned long long)tcap));
-    if (tot[0] == 0) return done(SEMTSDF_OK);  // no vertex, hence no triangle
+        return fail(SEMTSDF_ERR_INVALID, "mesh of %llu vertices and %llu triangles exceeds the capacities %llu, %llu",
+                    tot[0], tot[1], (unsigned long long)vcap, (unsigned long long)tcap);
+    if (tot[0] == 0) return SEMTSDF_OK;  // no vertex, hence no triangle
     off = 0;
     const uint64_t o_vtab = carve(v->g.nvox * sizeof(uint32_t)), o_verts = carve(tot[0] * sizeof(MeshVertexRec)),
                    o_tris = carve(tot[1] * 3 * sizeof(uint32_t));
-    if (int rc = alloc(&emit_d, off)) return done(rc);
+    if (int rc = emit_s.alloc(off)) return rc;
+    char* emit_d = emit_s.get<char>();
     uint32_t* vtab_d = (uint32_t*)(emit_d + o_vtab);
     MeshVertexRec* verts_d = (MeshVertexRec*)(emit_d + o_verts);
     uint32_t* tris_d = (uint32_t*)(emit_d + o_tris);
@@ -2387,8 +2282,8 @@ int semtsdf_extract_mesh(semtsdf_vol* v, int32_t min_weight, semtsdf_mesh_vertex
     if (e == hipSuccess) e = hipMemcpyAsync(verts, verts_d, tot[0] * sizeof(MeshVertexRec), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(tris, tris_d, tot[1] * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return done(fail(SEMTSDF_ERR_HIP, "mesh emit: %s", hipGetErrorString(e)));
-    return done(SEMTSDF_OK);
+    if (e != hipSuccess) return fail(SEMTSDF_ERR_HIP, "mesh emit: %s", hipGetErrorString(e));
+    return SEMTSDF_OK;
 }
 
 int semtsdf_instance_stats(semtsdf_vol* v, float sdf_max, int32_t min_weight, semtsdf_instance* out,
@@ -2401,19 +2296,14 @@ int semtsdf_instance_stats(semtsdf_vol* v, float sdf_max, int32_t min_weight, se
     hipStream_t s = v->stream;
     if (int rc = after_maps(v, s)) return rc;
     constexpr size_t rec_bytes = kMaxObjects * sizeof(InstanceRec), ov_bytes = kMaxObjects * kMaxObjects * sizeof(uint64_t);
-    char* scratch = nullptr;  // the records, then the overlap table
-    hipError_t e = hipMalloc((void**)&scratch, rec_bytes + ov_bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();  // the handle stays usable
-        return fail(e == hipErrorOutOfMemory ? SEMTSDF_ERR_OOM : SEMTSDF_ERR_HIP, "instance stats scratch: %s",
-                    hipGetErrorString(e));
-    }
+    Scratch guard;  // the records, then the overlap table
+    if (int rc = guard.alloc(rec_bytes + ov_bytes)) return rc;
+    char* scratch = guard.get<char>();
     unsigned long long* ov_d = overlap ? (unsigned long long*)(scratch + rec_bytes) : nullptr;
-    e = launch_instance_stats(v->g, v->b, sdf_max, min_weight, v->color_wide ? 1 : 0, (InstanceRec*)scratch, ov_d, s);
+    hipError_t e = launch_instance_stats(v->g, v->b, sdf_max, min_weight, v->color_wide ? 1 : 0, (InstanceRec*)scratch, ov_d, s);
     if (e == hipSuccess) e = hipMemcpyAsync(out, scratch, rec_bytes, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && overlap) e = hipMemcpyAsync(overlap, ov_d, ov_bytes, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(scratch);
     if (e != hipSuccess) return fail(SEMTSDF_ERR_HIP, "instance stats: %s", hipGetErrorString(e));
     return SEMTSDF_OK;
 }
