@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/semtsdf.h"
+#include "semtsdf_cam.h"
 #include "semtsdf_internal.h"
 #include "semtsdf_own.h"
 #include "semtsdf_wscan.h"
@@ -62,6 +63,20 @@ struct HipRaw {
     static void free(void* p) { (void)hipFree(p); }
 };
 using Scratch = CallScratch<HipRaw>;  // device scratch of one call
+
+// Queues host <-> device copies on s in the order given; one with a null end is skipped.
+struct Copy { void* dst; const void* src; size_t bytes; };
+int queue_copies(hipStream_t s, hipMemcpyKind kind, std::initializer_list<Copy> copies) {
+    for (const Copy& c : copies)
+        if (c.dst && c.src) HIPC(hipMemcpyAsync(c.dst, c.src, c.bytes, kind, s));
+    return SEMTSDF_OK;
+}
+// The end of a host-pointer variant: its results to the host, and s idle (the borrowed buffers are free).
+int copies_out(hipStream_t s, std::initializer_list<Copy> copies) {
+    if (int rc = queue_copies(s, hipMemcpyDeviceToHost, copies)) return rc;
+    HIPC(hipStreamSynchronize(s));
+    return SEMTSDF_OK;
+}
 
 // Palette of viewer.cu:93-126 (RGB triplets; written as BGR, viewer.cu:272).
 const uint8_t kPalette[kMaxObjects * 3] = {
@@ -386,10 +401,7 @@ int integrate_impl(semtsdf_vol* v, const uint16_t* depth_d, const uint8_t* rgb_d
     a.g = v->g;
     a.b = v->b;
     fill_E(a.E, E);
-    const float* K = v->p.K;
-    a.K[0] = K[0]; a.K[1] = K[1]; a.K[2] = K[2];
-    a.K[3] = K[4]; a.K[4] = K[5]; a.K[5] = K[6];
-    a.K[6] = K[8]; a.K[7] = K[9]; a.K[8] = K[10];
+    cam_mat3(a.K, v->p.K);
     a.width = v->p.width;
     a.height = v->p.height;
     a.depth_scale = v->p.depth_scale;
@@ -527,22 +539,26 @@ int integrate_impl(semtsdf_vol* v, const uint16_t* depth_d, const uint8_t* rgb_d
 }
 
 MarchCamera assoc_camera(const semtsdf_vol* v, const float E[16]) {
-    MarchCamera c{};
-    const float* Ki = v->p.Kinv;
-    c.Kinv[0] = Ki[0]; c.Kinv[1] = Ki[1]; c.Kinv[2] = Ki[2];
-    c.Kinv[3] = Ki[4]; c.Kinv[4] = Ki[5]; c.Kinv[5] = Ki[6];
-    c.Kinv[6] = Ki[8]; c.Kinv[7] = Ki[9]; c.Kinv[8] = Ki[10];
-    // Rt = E(0:3,0:3)^T, o = -Rt * t (tsdf.cu:432-435); the product is accumulated in
-    // double and rounded once, like cv::gemm on CV_32F.
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) c.Rt[i * 3 + j] = E[j * 4 + i];
-    for (int i = 0; i < 3; ++i) {
-        const double acc = (double)c.Rt[i * 3 + 0] * (double)E[3] + (double)c.Rt[i * 3 + 1] * (double)E[7] +
-                           (double)c.Rt[i * 3 + 2] * (double)E[11];
-        c.o[i] = -(float)acc;
-    }
-    c.use_s2w = 0;
+    MarchCamera c{};  // marches with Kinv, Rt and o, not with s2w
+    cam_mat3(c.Kinv, v->p.Kinv);
+    cam_rt(c.Rt, E);
+    cam_origin_assoc(c.o, E);
     return c;
+}
+
+// Arguments of the association march of mask_d at pose E (the tables as scratch).
+AssocArgs assoc_args(const semtsdf_vol* v, const uint8_t* mask_d, const float E[16], uint32_t n_obs) {
+    AssocArgs a{};
+    a.g = v->g;
+    a.b = v->b;
+    a.cam = assoc_camera(v, E);
+    a.width = v->p.width; a.height = v->p.height;
+    a.n_obs = (float)n_obs;
+    a.eps = v->p.prior_mrcnn_err_rate;
+    a.box_thresh = v->p.box_thresh;
+    a.mask = mask_d;
+    a.tables = v->tables_d;
+    return a;
 }
 
 // Orders stream s after the last empty-space map update.  On the stream that ran it nothing
@@ -628,17 +644,7 @@ int associate_impl(semtsdf_vol* v, uint8_t* mask_d, const float E[16], hipStream
     if (int rc = ensure_maps(v, s)) return rc;
     if (int rc = tables_ready(v, s)) return rc;
     HIPC(launch_mask_stats(mask_d, (int)npx(v), v->tables_d, s));
-    AssocArgs a{};
-    a.g = v->g;
-    a.b = v->b;
-    a.cam = assoc_camera(v, E);
-    a.width = v->p.width;
-    a.height = v->p.height;
-    a.n_obs = (float)v->n_obs;
-    a.eps = v->p.prior_mrcnn_err_rate;
-    a.box_thresh = v->p.box_thresh;
-    a.mask = mask_d;
-    a.tables = v->tables_d;
+    AssocArgs a = assoc_args(v, mask_d, E, v->n_obs);
     a.px = v->px;
     int order_n = 0;  // the decision orders the fused march's next launch (largest tiles first)
     if (view) {
@@ -695,6 +701,39 @@ void decision_to_stats(const AssocDecision& d, semtsdf_assoc_stats* st) {
     memcpy(st->lut, d.lut, 256);
 }
 
+// The label step of a semantic frame: the first frame's mask sets the object count (tsdf.cu:463-468),
+// a later frame's mask is associated with the model (arguments as associate_impl's).
+int frame_labels(semtsdf_vol* v, uint8_t* mask_d, const float E[16], hipStream_t s, bool want_decision,
+                 bool defer_relabel, const RenderArgs* view) {
+    if (v->n_obs > 0) return associate_impl(v, mask_d, E, s, want_decision, defer_relabel, view);
+    if (int rc = tables_ready(v, s)) return rc;
+    HIPC(launch_mask_stats(mask_d, (int)npx(v), v->tables_d, s));
+    HIPC(launch_first_frame_objs(v->tables_d, v->num_objs_d, s));
+    return SEMTSDF_OK;
+}
+
+// The tail of a decision queued on s, when stats are asked for: copied to the host (copy = false:
+// associate_impl's want_decision has queued that), awaited and reported.
+int report_decision(semtsdf_vol* v, hipStream_t s, semtsdf_assoc_stats* stats, bool copy = true) {
+    if (!stats) return SEMTSDF_OK;
+    if (copy) HIPC(hipMemcpyAsync(v->decision_h, v->decision_d, sizeof(AssocDecision), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    decision_to_stats(*v->decision_h, stats);
+    return SEMTSDF_OK;
+}
+
+// What a first semantic frame (no association) reports: no id moved, none matched, the object count.
+int first_frame_stats(semtsdf_vol* v, semtsdf_assoc_stats* stats) {
+    memset(stats, 0, sizeof(*stats));
+    for (int i = 0; i < kMaxObjects; ++i) stats->assigned_prev[i] = -1;
+    for (int i = 0; i < 256; ++i) stats->lut[i] = (uint8_t)i;
+    int no = 0;
+    HIPC(hipMemcpy(&no, v->num_objs_d, sizeof(int), hipMemcpyDeviceToHost));
+    stats->num_objs = no;
+    stats->max_obj_now = no;
+    return SEMTSDF_OK;
+}
+
 int validate_mask_host(const semtsdf_vol* v, const uint8_t* mask) {
     const size_t n = npx(v);
     for (size_t i = 0; i < n; ++i)
@@ -709,8 +748,7 @@ int validate_mask_host(const semtsdf_vol* v, const uint8_t* mask) {
 // been applied in full (the handle stays usable).
 int check_bad_label(semtsdf_vol* v, hipStream_t s) {
     unsigned long long c[3];
-    HIPC(hipMemcpyAsync(c, v->counters_d, sizeof(c), hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
+    if (int rc = copies_out(s, {{c, v->counters_d, sizeof(c)}})) return rc;
     if (c[2] != v->votes_dropped_seen) {
         const unsigned long long d = c[2] - v->votes_dropped_seen;
         v->votes_dropped_seen = c[2];
@@ -718,6 +756,17 @@ int check_bad_label(semtsdf_vol* v, hipStream_t s) {
                     "voxel's bins; SEMTSDF_F_ID_SATURATE avoids such ids)", d, kMaxObjects);
     }
     return SEMTSDF_OK;
+}
+
+// The end of a synchronous semantic frame, once it is applied in full: check_bad_label runs in every
+// case (it takes note of the votes this frame dropped); the entry's own label error (rc_own from
+// fail(), its message standing) is reported before the dropped votes.
+int label_epilogue(semtsdf_vol* v, hipStream_t s, int rc_own) {
+    const std::string own = rc_own ? g_err : std::string();
+    const int rc_votes = check_bad_label(v, s);
+    if (!rc_own) return rc_votes;
+    g_err = own;
+    return rc_own;
 }
 
 }  // namespace
@@ -1077,9 +1126,8 @@ int semtsdf_get_state(const semtsdf_vol* v, semtsdf_state* out) {
     if (!v || !out) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
     int n = 0;
     unsigned long long dropped = 0;
-    HIPC(hipMemcpyAsync(&n, v->num_objs_d, sizeof(int), hipMemcpyDeviceToHost, v->stream));
-    HIPC(hipMemcpyAsync(&dropped, v->counters_d + 2, sizeof(dropped), hipMemcpyDeviceToHost, v->stream));
-    HIPC(hipStreamSynchronize(v->stream));
+    if (int rc = copies_out(v->stream, {{&n, v->num_objs_d, sizeof(int)}, {&dropped, v->counters_d + 2, sizeof(dropped)}}))
+        return rc;
     out->n_obs = v->n_obs;
     out->num_objs = n;
     out->local_dim[0] = v->g.dimx;
@@ -1136,18 +1184,32 @@ int semtsdf_reset(semtsdf_vol* v, void* stream) {
 // sets num_objs = max(mask) + 1 (tsdf.cu:463-468): the split calls (associate, then integrate)
 // leave the state TSDF::parse_frame leaves, and an association never sees histogram counts
 // above n_obs that the reference could not produce (r06).  Before the frame's
-// integrate: the first frame's object count.
+// integrate: the first frame's object count (later frames: nothing).
 static int observe_before(semtsdf_vol* v, const uint8_t* mask_d, hipStream_t s) {
     if (!(v->p.flags & SEMTSDF_F_SEMANTIC) || v->n_obs > 0) return SEMTSDF_OK;
     if (!mask_d) return fail(SEMTSDF_ERR_INVALID, "semantic volume needs a mask");
-    if (int rc = tables_ready(v, s)) return rc;
-    HIPC(launch_mask_stats(mask_d, (int)npx(v), v->tables_d, s));
-    HIPC(launch_first_frame_objs(v->tables_d, v->num_objs_d, s));
-    return SEMTSDF_OK;
+    return frame_labels(v, const_cast<uint8_t*>(mask_d), nullptr, s, false, false, nullptr);  // reads the mask only
 }
 // ... and after it (only when it was enqueued: a failed integrate leaves n_obs alone)
 static void observe_after(semtsdf_vol* v) {
     if (v->p.flags & SEMTSDF_F_SEMANTIC) v->n_obs++;
+}
+// The device-resident frame of the split calls: observed, integrated, counted.
+static int integrate_observed(semtsdf_vol* v, const uint16_t* depth_d, const uint8_t* rgb_d, const uint8_t* mask_d,
+                              const float E[16], void* stream, bool async, void* inputs_ready) {
+    if (!v) return fail(SEMTSDF_ERR_INVALID, "NULL handle");
+    HIPC(hipSetDevice(v->device));
+    hipStream_t s = pick(v, stream);
+    if (int rc = observe_before(v, mask_d, s)) return rc;
+    if (int rc = integrate_impl(v, depth_d, rgb_d, mask_d, nullptr, E, s, async, (hipEvent_t)inputs_ready)) return rc;
+    observe_after(v);
+    return SEMTSDF_OK;
+}
+
+// The frame's images, and the mask when there is one, to the handle's staging.
+static int upload_frame(semtsdf_vol* v, const uint16_t* depth, const uint8_t* rgb, const uint8_t* mask, hipStream_t s) {
+    const size_t n = npx(v);
+    return queue_copies(s, hipMemcpyHostToDevice, {{v->depth_d, depth, n * 2}, {v->rgb_d, rgb, n * 3}, {v->mask_d, mask, n}});
 }
 
 int semtsdf_integrate(semtsdf_vol* v, const uint16_t* depth, const uint8_t* rgb, const uint8_t* mask,
@@ -1155,7 +1217,6 @@ int semtsdf_integrate(semtsdf_vol* v, const uint16_t* depth, const uint8_t* rgb,
     if (!v || !depth || !rgb) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
     HIPC(hipSetDevice(v->device));
     hipStream_t s = pick(v, stream);
-    const size_t n = npx(v);
     const bool sem = v->p.flags & SEMTSDF_F_SEMANTIC;
     bool past_bins = false;  // a label >= 32 in the mask
     if (sem) {
@@ -1170,42 +1231,26 @@ int semtsdf_integrate(semtsdf_vol* v, const uint16_t* depth, const uint8_t* rgb,
             past_bins = validate_mask_host(v, mask) != SEMTSDF_OK;
         }
     }
-    HIPC(hipMemcpyAsync(v->depth_d, depth, n * 2, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(v->rgb_d, rgb, n * 3, hipMemcpyHostToDevice, s));
-    if (sem) HIPC(hipMemcpyAsync(v->mask_d, mask, n, hipMemcpyHostToDevice, s));
+    if (int rc = upload_frame(v, depth, rgb, sem ? mask : nullptr, s)) return rc;
     if (int rc = observe_before(v, sem ? v->mask_d : nullptr, s)) return rc;
-    int rc = integrate_impl(v, v->depth_d, v->rgb_d, sem ? v->mask_d : nullptr, nullptr, E, s);
-    if (rc) return rc;
+    if (int rc = integrate_impl(v, v->depth_d, v->rgb_d, sem ? v->mask_d : nullptr, nullptr, E, s)) return rc;
     observe_after(v);
     HIPC(hipStreamSynchronize(s));  // host buffers are borrowed for the call only
     if (!sem) return SEMTSDF_OK;
-    const int rc_votes = check_bad_label(v, s);  // takes note of the votes this frame dropped
-    if (past_bins)
-        return fail(SEMTSDF_ERR_LABEL, "mask labels >= %d have no histogram bin: their votes were dropped, the "
-                    "frame was applied (SEMTSDF_F_ID_SATURATE keeps ids below %d)", kMaxObjects, kMaxObjects);
-    return rc_votes;
+    const int rc = !past_bins ? SEMTSDF_OK
+                              : fail(SEMTSDF_ERR_LABEL, "mask labels >= %d have no histogram bin: their votes were dropped, the "
+                                     "frame was applied (SEMTSDF_F_ID_SATURATE keeps ids below %d)", kMaxObjects, kMaxObjects);
+    return label_epilogue(v, s, rc);
 }
 
 int semtsdf_integrate_dev(semtsdf_vol* v, const uint16_t* depth_d, const uint8_t* rgb_d, const uint8_t* mask_d,
                           const float E[16], void* stream) {
-    if (!v) return fail(SEMTSDF_ERR_INVALID, "NULL handle");
-    HIPC(hipSetDevice(v->device));
-    hipStream_t s = pick(v, stream);
-    if (int rc = observe_before(v, mask_d, s)) return rc;
-    if (int rc = integrate_impl(v, depth_d, rgb_d, mask_d, nullptr, E, s)) return rc;
-    observe_after(v);
-    return SEMTSDF_OK;
+    return integrate_observed(v, depth_d, rgb_d, mask_d, E, stream, false, nullptr);
 }
 
 int semtsdf_integrate_dev_async(semtsdf_vol* v, const uint16_t* depth_d, const uint8_t* rgb_d, const uint8_t* mask_d,
                                 const float E[16], void* inputs_ready, void* stream) {
-    if (!v) return fail(SEMTSDF_ERR_INVALID, "NULL handle");
-    HIPC(hipSetDevice(v->device));
-    hipStream_t s = pick(v, stream);
-    if (int rc = observe_before(v, mask_d, s)) return rc;
-    if (int rc = integrate_impl(v, depth_d, rgb_d, mask_d, nullptr, E, s, true, (hipEvent_t)inputs_ready)) return rc;
-    observe_after(v);
-    return SEMTSDF_OK;
+    return integrate_observed(v, depth_d, rgb_d, mask_d, E, stream, true, inputs_ready);
 }
 
 int semtsdf_integrate_vote_dev(semtsdf_vol* v, const uint16_t* depth_d, const uint8_t* rgb_d, const int32_t* cls_d,
@@ -1219,14 +1264,11 @@ int semtsdf_associate(semtsdf_vol* v, uint8_t* mask_inout, const float E[16], se
                       void* stream) {
     if (!v || !mask_inout || !E) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
     HIPC(hipSetDevice(v->device));
-    int rc = validate_mask_host(v, mask_inout);
-    if (rc) return rc;
+    if (int rc = validate_mask_host(v, mask_inout)) return rc;
     hipStream_t s = pick(v, stream);
-    HIPC(hipMemcpyAsync(v->mask_d, mask_inout, npx(v), hipMemcpyHostToDevice, s));
-    rc = associate_impl(v, v->mask_d, E, s, true);
-    if (rc) return rc;
-    HIPC(hipMemcpyAsync(mask_inout, v->mask_d, npx(v), hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
+    if (int rc = queue_copies(s, hipMemcpyHostToDevice, {{v->mask_d, mask_inout, npx(v)}})) return rc;
+    if (int rc = associate_impl(v, v->mask_d, E, s, true)) return rc;
+    if (int rc = copies_out(s, {{mask_inout, v->mask_d, npx(v)}})) return rc;
     if (stats) decision_to_stats(*v->decision_h, stats);
     if (v->decision_h->bad_label)
         return fail(SEMTSDF_ERR_LABEL, "association produced %d objects (> %d)", v->decision_h->num_objs_after,
@@ -1238,13 +1280,8 @@ int semtsdf_associate_dev(semtsdf_vol* v, uint8_t* mask_d, const float E[16], se
                           void* stream) {
     if (!v || !mask_d || !E) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
     hipStream_t s = pick(v, stream);
-    int rc = associate_impl(v, mask_d, E, s, stats != nullptr);
-    if (rc) return rc;
-    if (stats) {
-        HIPC(hipStreamSynchronize(s));
-        decision_to_stats(*v->decision_h, stats);
-    }
-    return SEMTSDF_OK;
+    if (int rc = associate_impl(v, mask_d, E, s, stats != nullptr)) return rc;
+    return report_decision(v, s, stats, false);
 }
 
 int semtsdf_filter_overlaps_dev(semtsdf_vol* v, const float* probs_d, const uint8_t* box_d, uint8_t* mask_d,
@@ -1262,12 +1299,7 @@ int semtsdf_filter_overlaps_dev(semtsdf_vol* v, const float* probs_d, const uint
     HIPC(launch_assoc_decide(decide_args(v, mask_d, v->px), s));
     v->tables_clean = true;
     HIPC(launch_relabel(mask_d, (int)npx(v), v->decision_d, s));
-    if (stats) {
-        HIPC(hipMemcpyAsync(v->decision_h, v->decision_d, sizeof(AssocDecision), hipMemcpyDeviceToHost, s));
-        HIPC(hipStreamSynchronize(s));
-        decision_to_stats(*v->decision_h, stats);
-    }
-    return SEMTSDF_OK;
+    return report_decision(v, s, stats);
 }
 
 int semtsdf_libm_eval(int fn, const float* x_d, float* y_d, size_t n, void* stream) {
@@ -1290,25 +1322,12 @@ int semtsdf_assoc_probs(semtsdf_vol* v, const float E[16], float* probs, uint8_t
     HIPC(hipMemsetAsync(v->mask_d, 0, npx(v), s));
     HIPC(hipMemsetAsync(v->tables_d, 0, sizeof(AssocTables), s));
     v->tables_clean = false;
-    AssocArgs a{};
-    a.g = v->g;
-    a.b = v->b;
-    a.cam = assoc_camera(v, E);
-    a.width = v->p.width;
-    a.height = v->p.height;
-    a.n_obs = (float)(v->n_obs ? v->n_obs : 1);
-    a.eps = v->p.prior_mrcnn_err_rate;
-    a.box_thresh = v->p.box_thresh;
-    a.mask = v->mask_d;
-    a.tables = v->tables_d;
+    if (int rc = ensure_maps(v, s)) return rc;
+    AssocArgs a = assoc_args(v, v->mask_d, E, v->n_obs ? v->n_obs : 1);
     a.probs_out = v->probs_d;
     a.box_out = v->box_d;
-    if (int rc = ensure_maps(v, s)) return rc;
     HIPC(launch_assoc_march(a, s));
-    HIPC(hipMemcpyAsync(probs, v->probs_d, n * 4, hipMemcpyDeviceToHost, s));
-    HIPC(hipMemcpyAsync(box_mask, v->box_d, n, hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    return SEMTSDF_OK;
+    return copies_out(s, {{probs, v->probs_d, n * 4}, {box_mask, v->box_d, n}});
 }
 
 // An integrate that failed before its prepass leaves the association's deferred relabel
@@ -1327,31 +1346,18 @@ int semtsdf_parse_frame(semtsdf_vol* v, const uint16_t* depth, const uint8_t* rg
     if (!v || !depth || !rgb || !E) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
     HIPC(hipSetDevice(v->device));
     hipStream_t s = pick(v, stream);
-    const size_t n = npx(v);
     const bool sem = v->p.flags & SEMTSDF_F_SEMANTIC;
     if (sem) {
         if (!mask_inout) return fail(SEMTSDF_ERR_INVALID, "semantic volume needs a mask");
-        int rc = validate_mask_host(v, mask_inout);
-        if (rc) return rc;
+        if (int rc = validate_mask_host(v, mask_inout)) return rc;
     }
-    HIPC(hipMemcpyAsync(v->depth_d, depth, n * 2, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(v->rgb_d, rgb, n * 3, hipMemcpyHostToDevice, s));
-    if (sem) {
-        HIPC(hipMemcpyAsync(v->mask_d, mask_inout, n, hipMemcpyHostToDevice, s));
-        if (v->n_obs > 0) {
-            int rc = associate_impl(v, v->mask_d, E, s, true, true);
-            if (rc) return rc;
-        } else {
-            if (int rc = tables_ready(v, s)) return rc;
-            HIPC(launch_mask_stats(v->mask_d, (int)n, v->tables_d, s));
-            HIPC(launch_first_frame_objs(v->tables_d, v->num_objs_d, s));
-        }
-    }
+    if (int rc = upload_frame(v, depth, rgb, sem ? mask_inout : nullptr, s)) return rc;
+    if (sem)
+        if (int rc = frame_labels(v, v->mask_d, E, s, true, true, nullptr)) return rc;
     int rc = integrate_impl(v, v->depth_d, v->rgb_d, sem ? v->mask_d : nullptr, nullptr, E, s);
     if (rc) return relabel_unconsumed(v, v->mask_d, s, rc);
     v->n_obs++;
-    if (sem) HIPC(hipMemcpyAsync(mask_inout, v->mask_d, n, hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
+    if ((rc = copies_out(s, {{sem ? mask_inout : nullptr, v->mask_d, npx(v)}}))) return rc;
     int rc_label = SEMTSDF_OK;  // reported after the frame is applied in full (the handle stays usable)
     if (sem && v->n_obs > 1) {
         if (stats) decision_to_stats(*v->decision_h, stats);
@@ -1360,19 +1366,9 @@ int semtsdf_parse_frame(semtsdf_vol* v, const uint16_t* depth, const uint8_t* rg
                             "histogram bin (SEMTSDF_F_ID_SATURATE avoids them)", v->decision_h->num_objs_after,
                             kMaxObjects, kMaxObjects);
     } else if (stats) {
-        memset(stats, 0, sizeof(*stats));
-        for (int i = 0; i < kMaxObjects; ++i) stats->assigned_prev[i] = -1;
-        for (int i = 0; i < 256; ++i) stats->lut[i] = (uint8_t)i;
-        int no = 0;
-        HIPC(hipMemcpy(&no, v->num_objs_d, sizeof(int), hipMemcpyDeviceToHost));
-        stats->num_objs = no;
-        stats->max_obj_now = no;
+        if ((rc = first_frame_stats(v, stats))) return rc;
     }
-    if (sem) {
-        const int rc_votes = check_bad_label(v, s);  // also takes note of this frame's dropped votes
-        return rc_label ? rc_label : rc_votes;
-    }
-    return SEMTSDF_OK;
+    return sem ? label_epilogue(v, s, rc_label) : SEMTSDF_OK;
 }
 
 int semtsdf_parse_frame_dev(semtsdf_vol* v, const uint16_t* depth_d, const uint8_t* rgb_d, uint8_t* mask_d,
@@ -1403,15 +1399,8 @@ static int parse_frame_dev_impl(semtsdf_vol* v, const uint16_t* depth_d, const u
         if (!v->in_ev) HIPC(hipEventCreateWithFlags(&v->in_ev, order_event_flags()));
         HIPC(hipEventRecord(v->in_ev, s));
     }
-    if (sem) {
-        if (v->n_obs > 0) {
-            if (int rc = associate_impl(v, mask_d, E, s, false, true, fused ? view : nullptr)) return rc;
-        } else {
-            if (int rc = tables_ready(v, s)) return rc;
-            HIPC(launch_mask_stats(mask_d, (int)npx(v), v->tables_d, s));
-            HIPC(launch_first_frame_objs(v->tables_d, v->num_objs_d, s));
-        }
-    }
+    if (sem)
+        if (int rc = frame_labels(v, mask_d, E, s, false, true, fused ? view : nullptr)) return rc;
     // the integrate is the frame's only write of the volume: readers of the previous state on
     // other streams (a live render) finish first; the association above, a read, may overlap them
     if (integrate_after_event) HIPC(hipStreamWaitEvent(s, (hipEvent_t)integrate_after_event, 0));
@@ -1442,7 +1431,7 @@ int semtsdf_parse_frame_view_dev(semtsdf_vol* v, const uint16_t* depth_d, const 
 }
 
 // ---- Z-sharded raycast protocol ------------------------------------------------------
-static ShardRayArgs shard_args(semtsdf_vol* v) {
+static ShardRayArgs shard_args(semtsdf_vol* v, const void* gathered_d) {
     ShardRayArgs a{};
     a.g = v->g;
     a.b = v->b;
@@ -1451,14 +1440,9 @@ static ShardRayArgs shard_args(semtsdf_vol* v) {
     a.height = v->p.height;
     a.kind = v->ray_kind;
     a.nrec = v->ray_nrec;
-    const size_t n = npx(v);
-    char* base = (char*)v->ray_state_d;
-    a.st.k = (int*)(base);
-    a.st.fk = (float*)(base + 4 * n);
-    a.st.j = (int*)(base + 8 * n);
-    a.st.fj = (float*)(base + 12 * n);
-    a.st.fp = (float*)(base + 16 * n);
-    a.st.t = (float*)(base + 20 * n);
+    a.gathered = (const int2*)gathered_d;
+    const RayScratch st{{v->ray_state_d, npx(v)}};
+    a.st = ShardRayState{st.k, st.fk, st.j, st.fj, st.fp, st.t};
     a.color_i32 = v->color_wide ? 1 : 0;
     a.palette = v->palette_d;
     a.n_obs = (float)v->n_obs;
@@ -1480,16 +1464,10 @@ int semtsdf_shard_ray_begin(semtsdf_vol* v, int kind, const float cam[16], const
     if (kind == SEMTSDF_RAY_ASSOC && v->n_obs == 0)
         return fail(SEMTSDF_ERR_STATE, "association needs n_obs > 0 (tsdf.cu:426)");
     HIPC(hipSetDevice(v->device));
-    if (int rc = v->ray_state_d ? 0 : v->pool.alloc(&v->ray_state_d, 24 * npx(v))) return rc;
-    if (kind == SEMTSDF_RAY_ASSOC) {
-        v->ray_cam = assoc_camera(v, cam);
-    } else {
-        MarchCamera m{};
-        for (int i = 0; i < 12; ++i) m.s2w[i] = cam[i];
-        m.o[0] = c[0]; m.o[1] = c[1]; m.o[2] = c[2];
-        m.use_s2w = 1;
-        v->ray_cam = m;
-    }
+    if (int rc = v->ray_state_d ? 0 : v->pool.alloc(&v->ray_state_d, RayScratch{{nullptr, npx(v)}}.bytes)) return rc;
+    v->ray_cam = MarchCamera{};
+    if (kind == SEMTSDF_RAY_ASSOC) v->ray_cam = assoc_camera(v, cam);
+    else cam_view(v->ray_cam, cam, c);
     if (int rc = ensure_maps(v, v->stream)) return rc;
     HIPC(hipStreamSynchronize(v->stream));  // the protocol's steps may run on another stream
     v->ray_kind = kind;
@@ -1510,9 +1488,8 @@ int semtsdf_shard_ray_step(semtsdf_vol* v, int step, const void* gathered_d, voi
     if (step > 0 && !gathered_d) return fail(SEMTSDF_ERR_INVALID, "step %d needs the gathered records", step);
     HIPC(hipSetDevice(v->device));
     hipStream_t s = pick(v, stream);
-    ShardRayArgs a = shard_args(v);
+    ShardRayArgs a = shard_args(v, gathered_d);
     a.step = step;
-    a.gathered = (const int2*)gathered_d;
     a.send = (int2*)send_d;
     EventPair ep;
     timing_begin(v, v->ray_kind == SEMTSDF_RAY_ASSOC ? v->ev_assoc : v->ev_render, s, &ep);
@@ -1531,8 +1508,7 @@ int semtsdf_shard_render_finish(semtsdf_vol* v, const void* gathered_d, uint8_t*
     if (v->ray_next != 4) return fail(SEMTSDF_ERR_STATE, "render_finish before step 3");
     HIPC(hipSetDevice(v->device));
     hipStream_t s = pick(v, stream);
-    ShardRayArgs a = shard_args(v);
-    a.gathered = (const int2*)gathered_d;
+    ShardRayArgs a = shard_args(v, gathered_d);
     a.out_bgr = out_bgr_d;
     a.out_t = out_t_d;
     HIPC(launch_shard_render_finish(a, s));
@@ -1548,8 +1524,7 @@ int semtsdf_shard_assoc_partial(semtsdf_vol* v, const void* gathered_d, const ui
         return fail(SEMTSDF_ERR_STATE, "assoc_partial needs the three association steps first");
     HIPC(hipSetDevice(v->device));
     hipStream_t s = pick(v, stream);
-    ShardRayArgs a = shard_args(v);
-    a.gathered = (const int2*)gathered_d;
+    ShardRayArgs a = shard_args(v, gathered_d);
     a.mask = mask_d;
     a.partial = (long long*)partial_d;
     EventPair ep;
@@ -1567,70 +1542,55 @@ int semtsdf_shard_assoc_pixels(semtsdf_vol* v, const void* gathered_d, int32_t* 
     if (!v->assoc_ray_done) return fail(SEMTSDF_ERR_STATE, "assoc_pixels needs a completed association protocol");
     HIPC(hipSetDevice(v->device));
     hipStream_t s = pick(v, stream);
-    ShardRayArgs a = shard_args(v);
+    ShardRayArgs a = shard_args(v, gathered_d);
     a.kind = SEMTSDF_RAY_ASSOC;  // the protocol's kind (assoc_partial has closed it)
-    a.gathered = (const int2*)gathered_d;
     HIPC(launch_shard_assoc_pixels(a, px_d, s));
     return SEMTSDF_OK;
+}
+
+// The decision of a sharded association from the reduced sums: statistics, tables from the partial
+// sums, decide, relabel.  px_d: every pixel's data (semtsdf_shard_assoc_pixels); without it the
+// certificate runs first, and rows it cannot decide from the sums end the call with NEED_PIXELS.
+static int shard_apply(semtsdf_vol* v, const int64_t* reduced_d, const int32_t* px_d, uint8_t* mask_d,
+                       semtsdf_assoc_stats* stats, void* stream) {
+    HIPC(hipSetDevice(v->device));
+    hipStream_t s = pick(v, stream);
+    EventPair ep;
+    timing_begin(v, v->ev_assoc, s, &ep);
+    if (int rc = tables_ready(v, s)) return rc;
+    HIPC(launch_mask_stats(mask_d, (int)npx(v), v->tables_d, s));
+    HIPC(launch_tables_from_partial((const long long*)reduced_d, v->tables_d, s));
+    AssocPixels px{};
+    if (px_d) {
+        px.bits = reinterpret_cast<uint2*>(const_cast<int32_t*>(px_d));
+        px.p = reinterpret_cast<float*>(const_cast<int32_t*>(px_d) + 2 * npx(v));
+    } else {
+        HIPC(launch_assoc_decide(decide_args(v, mask_d, px, true), s));
+        unsigned missing = 0;
+        if (int rc = copies_out(s, {{&missing, &v->decision_d->exact_missing, sizeof(unsigned)}})) return rc;
+        if (missing) {
+            timing_end(v, v->ev_assoc, s, &ep);
+            return SEMTSDF_NEED_PIXELS;  // the tables stay filled for semtsdf_shard_assoc_apply_exact
+        }
+    }
+    HIPC(launch_assoc_decide(decide_args(v, mask_d, px), s));
+    v->tables_clean = true;  // the decide kernel clears them
+    HIPC(launch_relabel(mask_d, (int)npx(v), v->decision_d, s));
+    timing_end(v, v->ev_assoc, s, &ep);
+    v->n_assoc++;
+    return report_decision(v, s, stats);
 }
 
 int semtsdf_shard_assoc_apply_exact(semtsdf_vol* v, const int64_t* reduced_d, const int32_t* px_d, uint8_t* mask_d,
                                     semtsdf_assoc_stats* stats, void* stream) {
     if (!v || !reduced_d || !px_d || !mask_d) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
-    HIPC(hipSetDevice(v->device));
-    hipStream_t s = pick(v, stream);
-    EventPair ep;
-    timing_begin(v, v->ev_assoc, s, &ep);
-    if (int rc = tables_ready(v, s)) return rc;
-    HIPC(launch_mask_stats(mask_d, (int)npx(v), v->tables_d, s));
-    HIPC(launch_tables_from_partial((const long long*)reduced_d, v->tables_d, s));
-    AssocPixels px;
-    px.bits = reinterpret_cast<uint2*>(const_cast<int32_t*>(px_d));
-    px.p = reinterpret_cast<float*>(const_cast<int32_t*>(px_d) + 2 * npx(v));
-    HIPC(launch_assoc_decide(decide_args(v, mask_d, px), s));
-    v->tables_clean = true;
-    HIPC(launch_relabel(mask_d, (int)npx(v), v->decision_d, s));
-    timing_end(v, v->ev_assoc, s, &ep);
-    v->n_assoc++;
-    if (stats) {
-        HIPC(hipMemcpyAsync(v->decision_h, v->decision_d, sizeof(AssocDecision), hipMemcpyDeviceToHost, s));
-        HIPC(hipStreamSynchronize(s));
-        decision_to_stats(*v->decision_h, stats);
-    }
-    return SEMTSDF_OK;
+    return shard_apply(v, reduced_d, px_d, mask_d, stats, stream);
 }
 
 int semtsdf_shard_assoc_apply(semtsdf_vol* v, const int64_t* reduced_d, uint8_t* mask_d, semtsdf_assoc_stats* stats,
                               void* stream) {
     if (!v || !reduced_d || !mask_d) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
-    HIPC(hipSetDevice(v->device));
-    hipStream_t s = pick(v, stream);
-    EventPair ep;
-    timing_begin(v, v->ev_assoc, s, &ep);
-    if (int rc = tables_ready(v, s)) return rc;
-    HIPC(launch_mask_stats(mask_d, (int)npx(v), v->tables_d, s));
-    HIPC(launch_tables_from_partial((const long long*)reduced_d, v->tables_d, s));
-    // the certificate first: rows it cannot decide from the reduced sums need every pixel's
-    // data, which the shards hold in parts (semtsdf_shard_assoc_pixels)
-    HIPC(launch_assoc_decide(decide_args(v, mask_d, AssocPixels{}, true), s));
-    unsigned missing = 0;
-    HIPC(hipMemcpyAsync(&missing, &v->decision_d->exact_missing, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    if (missing) {
-        timing_end(v, v->ev_assoc, s, &ep);
-        return SEMTSDF_NEED_PIXELS;  // the tables stay filled for semtsdf_shard_assoc_apply_exact
-    }
-    HIPC(launch_assoc_decide(decide_args(v, mask_d, AssocPixels{}), s));
-    v->tables_clean = true;  // the decide kernel clears them
-    HIPC(launch_relabel(mask_d, (int)npx(v), v->decision_d, s));
-    timing_end(v, v->ev_assoc, s, &ep);
-    v->n_assoc++;
-    if (stats) {
-        HIPC(hipMemcpyAsync(v->decision_h, v->decision_d, sizeof(AssocDecision), hipMemcpyDeviceToHost, s));
-        HIPC(hipStreamSynchronize(s));
-        decision_to_stats(*v->decision_h, stats);
-    }
-    return SEMTSDF_OK;
+    return shard_apply(v, reduced_d, nullptr, mask_d, stats, stream);
 }
 
 // ABI <= 11 advanced n_obs here after a sharded integrate; the integrate entry points do it
@@ -1685,8 +1645,7 @@ int semtsdf_detections_to_labels(const int32_t* boxes_d, const void* mini_d, int
                                      areas_d, s));
     if (n_kept) {
         unsigned k = 0;
-        HIPC(hipMemcpyAsync(&k, (char*)work_d + mask_scratch_kept_offset(), sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        HIPC(hipStreamSynchronize(s));
+        if (int rc = copies_out(s, {{&k, (char*)work_d + mask_scratch_kept_offset(), sizeof(unsigned)}})) return rc;
         *n_kept = (int)k;
     }
     return SEMTSDF_OK;
@@ -1756,11 +1715,8 @@ static int render_args(semtsdf_vol* v, const float s2w[16], const float c[3], in
     a = RenderArgs{};
     a.g = v->g;
     a.b = v->b;
-    for (int i = 0; i < 12; ++i) a.cam.s2w[i] = s2w[i];
-    a.cam.o[0] = c[0]; a.cam.o[1] = c[1]; a.cam.o[2] = c[2];
-    a.cam.use_s2w = 1;
-    a.width = v->p.width;
-    a.height = v->p.height;
+    cam_view(a.cam, s2w, c);
+    a.width = v->p.width; a.height = v->p.height;
     a.mode = mode;
     a.color_i32 = v->color_wide ? 1 : 0;
     a.palette = v->palette_d;
@@ -1819,12 +1775,8 @@ int semtsdf_raycast(semtsdf_vol* v, const float s2w[16], const float c[3], int m
     const size_t n = npx(v);
     if (!v->render_d)
         if (int rc = v->pool.alloc_group({{(void**)&v->render_d, n * 3}, {(void**)&v->render_t_d, n * 4}})) return rc;
-    int rc = raycast_impl(v, s2w, c, mode, v->render_d, v->render_t_d, s);
-    if (rc) return rc;
-    HIPC(hipMemcpyAsync(out_bgr, v->render_d, n * 3, hipMemcpyDeviceToHost, s));
-    if (out_t) HIPC(hipMemcpyAsync(out_t, v->render_t_d, n * 4, hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    return SEMTSDF_OK;
+    if (int rc = raycast_impl(v, s2w, c, mode, v->render_d, v->render_t_d, s)) return rc;
+    return copies_out(s, {{out_bgr, v->render_d, n * 3}, {out_t, v->render_t_d, n * 4}});
 }
 
 int semtsdf_raycast_dev(semtsdf_vol* v, const float s2w[16], const float c[3], int mode, uint8_t* out_bgr_d,
@@ -1837,11 +1789,7 @@ int semtsdf_pose_camera(const float Kinv[16], const float E[16], float s2w[16], 
     if (!Kinv || !E || !s2w || !c) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
     // Rt = E[:3,:3]^T, o = -Rt E[:3,3], s2w = [Rt Kinv[:3,:3] | o]: sums of double products, rounded once
     float o[3];
-    for (int i = 0; i < 3; ++i) {
-        double acc = 0;
-        for (int k = 0; k < 3; ++k) acc += (double)E[k * 4 + i] * (double)E[k * 4 + 3];
-        o[i] = (float)(-acc);
-    }
+    cam_origin(o, E);
     for (int i = 0; i < 3; ++i) {
         for (int j = 0; j < 3; ++j) {
             double acc = 0;
@@ -1871,11 +1819,8 @@ static int maps_impl(semtsdf_vol* v, const float s2w[16], const float c[3], int3
                      const semtsdf_maps_out& out_d, hipStream_t s) {
     MapsArgs a{};
     a.g = v->g;
-    for (int i = 0; i < 12; ++i) a.cam.s2w[i] = s2w[i];
-    a.cam.o[0] = c[0]; a.cam.o[1] = c[1]; a.cam.o[2] = c[2];
-    a.cam.use_s2w = 1;
-    a.width = v->p.width;
-    a.height = v->p.height;
+    cam_view(a.cam, s2w, c);
+    a.width = v->p.width; a.height = v->p.height;
     a.min_weight = min_weight;
     a.t = out_d.t; a.point = out_d.point; a.normal = out_d.normal;
     a.label = out_d.label; a.votes = out_d.votes; a.flags = out_d.flags;
@@ -1901,32 +1846,21 @@ int semtsdf_render_maps(semtsdf_vol* v, const float s2w[16], const float c[3], i
     HIPC(hipSetDevice(v->device));
     hipStream_t s = pick(v, stream);
     const size_t n = npx(v);
-    // t, point, normal, votes (4-B aligned), then label and flags
-    if (int rc = v->maps_d ? 0 : v->pool.alloc((void**)&v->maps_d, n * 34)) return rc;
-    float* f = reinterpret_cast<float*>(v->maps_d);
-    semtsdf_maps_out d{};
-    d.t = out_host->t ? f : nullptr;
-    d.point = out_host->point ? f + n : nullptr;
-    d.normal = out_host->normal ? f + n * 4 : nullptr;
-    d.votes = out_host->votes ? f + n * 7 : nullptr;
-    d.label = out_host->label ? v->maps_d + n * 32 : nullptr;
-    d.flags = out_host->flags ? v->maps_d + n * 33 : nullptr;
+    if (int rc = v->maps_d ? 0 : v->pool.alloc((void**)&v->maps_d, MapsScratch{{nullptr, n}}.bytes)) return rc;
+    const MapsScratch m{{v->maps_d, n}};
+    const semtsdf_maps_out& h = *out_host;
+    semtsdf_maps_out d{};  // the maps asked for
+    d.t = h.t ? m.t : nullptr; d.point = h.point ? m.point : nullptr; d.normal = h.normal ? m.normal : nullptr;
+    d.votes = h.votes ? m.votes : nullptr; d.label = h.label ? m.label : nullptr; d.flags = h.flags ? m.flags : nullptr;
     if (int rc = maps_impl(v, s2w, c, min_weight, d, s)) return rc;
-    if (d.t) HIPC(hipMemcpyAsync(out_host->t, d.t, n * 4, hipMemcpyDeviceToHost, s));
-    if (d.point) HIPC(hipMemcpyAsync(out_host->point, d.point, n * 12, hipMemcpyDeviceToHost, s));
-    if (d.normal) HIPC(hipMemcpyAsync(out_host->normal, d.normal, n * 12, hipMemcpyDeviceToHost, s));
-    if (d.votes) HIPC(hipMemcpyAsync(out_host->votes, d.votes, n * 4, hipMemcpyDeviceToHost, s));
-    if (d.label) HIPC(hipMemcpyAsync(out_host->label, d.label, n, hipMemcpyDeviceToHost, s));
-    if (d.flags) HIPC(hipMemcpyAsync(out_host->flags, d.flags, n, hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    return SEMTSDF_OK;
+    return copies_out(s, {{h.t, d.t, n * 4}, {h.point, d.point, n * 12}, {h.normal, d.normal, n * 12},
+                          {h.votes, d.votes, n * 4}, {h.label, d.label, n}, {h.flags, d.flags, n}});
 }
 
 // ---- camera tracking: frame maps and the point-to-plane system ---------------------------------
-// Device scratch of the host-pointer variants, 52 B per pixel + the words: the 4-B aligned arrays
-// first (frame vertex, normal; model point, normal; the words), then the two flag maps and the depth.
+// Device scratch of the host-pointer variants (TrackScratch), allocated on the first use.
 static int track_scratch(semtsdf_vol* v) {
-    return v->track_d ? SEMTSDF_OK : v->pool.alloc((void**)&v->track_d, npx(v) * 52 + kIcpWords * 8);
+    return v->track_d ? 0 : v->pool.alloc((void**)&v->track_d, TrackScratch{{nullptr, npx(v)}, kIcpWords}.bytes);
 }
 
 static int frame_maps_check(semtsdf_vol* v, const uint16_t* depth, float* vertex, float* normal, uint8_t* flags) {
@@ -1940,14 +1874,10 @@ static int frame_maps_impl(semtsdf_vol* v, const uint16_t* depth_d, float* verte
                            uint8_t* flags_d, hipStream_t s) {
     FrameMapsArgs a{};
     a.depth = depth_d;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) a.Kinv[i * 3 + j] = v->p.Kinv[i * 4 + j];
+    cam_mat3(a.Kinv, v->p.Kinv);
     a.depth_scale = v->p.depth_scale;
-    a.width = v->p.width;
-    a.height = v->p.height;
-    a.vertex = vertex_d;
-    a.normal = normal_d;
-    a.flags = flags_d;
+    a.width = v->p.width; a.height = v->p.height;
+    a.vertex = vertex_d; a.normal = normal_d; a.flags = flags_d;
     HIPC(launch_frame_maps(a, s));
     return SEMTSDF_OK;
 }
@@ -1966,18 +1896,12 @@ int semtsdf_frame_maps(semtsdf_vol* v, const uint16_t* depth, float* vertex, flo
     hipStream_t s = pick(v, stream);
     const size_t n = npx(v);
     if (int rc = track_scratch(v)) return rc;
-    float* f = reinterpret_cast<float*>(v->track_d);
-    float* vertex_d = vertex ? f : nullptr;
-    float* normal_d = normal ? f + n * 3 : nullptr;
-    uint8_t* flags_d = flags ? v->track_d + n * 48 + kIcpWords * 8 : nullptr;
-    uint16_t* depth_d = reinterpret_cast<uint16_t*>(v->track_d + n * 50 + kIcpWords * 8);
-    HIPC(hipMemcpyAsync(depth_d, depth, n * 2, hipMemcpyHostToDevice, s));
-    if (int rc = frame_maps_impl(v, depth_d, vertex_d, normal_d, flags_d, s)) return rc;
-    if (vertex) HIPC(hipMemcpyAsync(vertex, vertex_d, n * 12, hipMemcpyDeviceToHost, s));
-    if (normal) HIPC(hipMemcpyAsync(normal, normal_d, n * 12, hipMemcpyDeviceToHost, s));
-    if (flags) HIPC(hipMemcpyAsync(flags, flags_d, n, hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    return SEMTSDF_OK;
+    const TrackScratch t{{v->track_d, n}, kIcpWords};
+    if (int rc = queue_copies(s, hipMemcpyHostToDevice, {{t.depth, depth, n * 2}})) return rc;
+    if (int rc = frame_maps_impl(v, t.depth, vertex ? t.vertex : nullptr, normal ? t.normal : nullptr,
+                                 flags ? t.flags : nullptr, s))
+        return rc;
+    return copies_out(s, {{vertex, t.vertex, n * 12}, {normal, t.normal, n * 12}, {flags, t.flags, n}});
 }
 
 // Argument checks of the system, all before any device work.
@@ -2004,21 +1928,12 @@ static int icp_impl(semtsdf_vol* v, const semtsdf_icp_in& in_d, const float E_re
     IcpArgs a{};
     a.vertex = in_d.vertex; a.normal = in_d.normal; a.flags = in_d.flags;
     a.m_point = in_d.m_point; a.m_normal = in_d.m_normal; a.m_flags = in_d.m_flags;
-    for (int i = 0; i < 3; ++i) {  // Rt, o of E_cur: semtsdf_pose_camera's sums of double products, rounded once
-        double acc = 0;
-        for (int k = 0; k < 3; ++k) acc += (double)E_cur[k * 4 + i] * (double)E_cur[k * 4 + 3];
-        a.o[i] = (float)(-acc);
-        for (int j = 0; j < 3; ++j) {
-            a.Rt[i * 3 + j] = E_cur[j * 4 + i];
-            a.K[i * 3 + j] = v->p.K[i * 4 + j];
-        }
-    }
+    cam_rt(a.Rt, E_cur);
+    cam_origin(a.o, E_cur);  // semtsdf_pose_camera's form
+    cam_mat3(a.K, v->p.K);
     fill_E(a.Eref, E_ref);
-    a.dmax2 = dist_max * dist_max;
-    a.cos_min = cos_min;
-    a.stride = stride;
-    a.width = v->p.width;
-    a.height = v->p.height;
+    a.dmax2 = dist_max * dist_max; a.cos_min = cos_min; a.stride = stride;
+    a.width = v->p.width; a.height = v->p.height;
     a.words = reinterpret_cast<long long*>(words_d);
     HIPC(hipMemsetAsync(words_d, 0, kIcpWords * 8, s));
     HIPC(launch_icp_system(a, s));
@@ -2040,20 +1955,15 @@ int semtsdf_icp_system(semtsdf_vol* v, const semtsdf_icp_in* in_host, const floa
     hipStream_t s = pick(v, stream);
     const size_t n = npx(v);
     if (int rc = track_scratch(v)) return rc;
-    float* f = reinterpret_cast<float*>(v->track_d);
-    uint8_t* b = v->track_d + n * 48 + kIcpWords * 8;
-    int64_t* words_d = reinterpret_cast<int64_t*>(v->track_d + n * 48);
-    HIPC(hipMemcpyAsync(f, in_host->vertex, n * 12, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(f + n * 3, in_host->normal, n * 12, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(f + n * 6, in_host->m_point, n * 12, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(f + n * 9, in_host->m_normal, n * 12, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(b, in_host->flags, n, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(b + n, in_host->m_flags, n, hipMemcpyHostToDevice, s));
-    semtsdf_icp_in d{f, f + n * 3, b, f + n * 6, f + n * 9, b + n};
-    if (int rc = icp_impl(v, d, E_ref, E_cur, dist_max, cos_min, stride, words_d, s)) return rc;
-    HIPC(hipMemcpyAsync(words_host, words_d, kIcpWords * 8, hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    return SEMTSDF_OK;
+    const TrackScratch t{{v->track_d, n}, kIcpWords};
+    const semtsdf_icp_in& h = *in_host;
+    if (int rc = queue_copies(s, hipMemcpyHostToDevice, {{t.vertex, h.vertex, n * 12}, {t.normal, h.normal, n * 12},
+                                                         {t.m_point, h.m_point, n * 12}, {t.m_normal, h.m_normal, n * 12},
+                                                         {t.flags, h.flags, n}, {t.m_flags, h.m_flags, n}}))
+        return rc;
+    semtsdf_icp_in d{t.vertex, t.normal, t.flags, t.m_point, t.m_normal, t.m_flags};
+    if (int rc = icp_impl(v, d, E_ref, E_cur, dist_max, cos_min, stride, t.words, s)) return rc;
+    return copies_out(s, {{words_host, t.words, kIcpWords * 8}});
 }
 
 // Voxels of the reference layout (rows of lz planes) held by the handle.
@@ -2179,9 +2089,7 @@ int semtsdf_map_words(semtsdf_vol* v, uint64_t* out, uint64_t capacity, uint64_t
     *count = (uint64_t)v->g.nbx * v->g.nby * v->g.nbz;
     if (int rc = ensure_maps(v, s)) return rc;  // the maps of the current state
     const uint64_t n = std::min<uint64_t>(capacity, *count);
-    if (out && n) HIPC(hipMemcpyAsync(out, v->b.boct, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    return SEMTSDF_OK;
+    return copies_out(s, {{n ? out : nullptr, v->b.boct, n * sizeof(uint64_t)}});
 }
 
 int semtsdf_export_surface(semtsdf_vol* v, float sdf_max, int32_t min_weight, semtsdf_surface_point* out,
@@ -2331,8 +2239,7 @@ int semtsdf_remap_instances(semtsdf_vol* v, const uint8_t* lut, int32_t num_objs
     if (int rc = after_maps(v, s)) return rc;
     // the current next id lives on the device (the decisions advance it there)
     int cur = 0;
-    HIPC(hipMemcpyAsync(&cur, v->num_objs_d, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
+    if (int rc = copies_out(s, {{&cur, v->num_objs_d, sizeof(int)}})) return rc;
     const int live = std::max(1, std::min(cur, kMaxObjects)), top = std::max(cur, 1);
     int need = 1;
     for (int k = 0; k < live; ++k) need = std::max(need, 1 + (int)lut[k]);
@@ -2469,9 +2376,8 @@ int semtsdf_tsdf_update(float* tsdf_diff, int32_t* tsdf_color, int32_t* tsdf_wt,
     if (rc) return rc;
     const size_t n = npx(v);
     hipStream_t s = v->stream;
-    HIPC(hipMemcpyAsync(v->depth_d, depth, n * 2, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(v->rgb_d, color, n * 3, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(v->cls_d, cls, n * 4, hipMemcpyHostToDevice, s));
+    rc = queue_copies(s, hipMemcpyHostToDevice, {{v->depth_d, depth, n * 2}, {v->rgb_d, color, n * 3}, {v->cls_d, cls, n * 4}});
+    if (rc) return rc;
     rc = integrate_impl(v, v->depth_d, v->rgb_d, nullptr, v->cls_d, extrinsic2init, s);
     if (rc) return rc;
     rc = semtsdf_download(v, tsdf_diff, tsdf_wt, tsdf_color, nullptr, tsdf_cls, tsdf_cls_cnt);

@@ -1,0 +1,92 @@
+// Camera set-up and staging layouts of the host API (semtsdf_api.cpp) on plain arrays.  Host code
+// only, no HIP: tests/helpers/api_parts_check.cpp compiles it alone.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+namespace semtsdf {
+
+// The 3x3 part of a row-major 4x4 (K, K^-1).
+inline void cam_mat3(float dst[9], const float m[16]) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) dst[i * 3 + j] = m[i * 4 + j];
+}
+
+// A view's camera (MarchCamera): rows 0..2 of screen-to-world, the centre as the ray origin.
+template <class Cam>
+void cam_view(Cam& m, const float s2w[16], const float c[3]) {
+    for (int i = 0; i < 12; ++i) m.s2w[i] = s2w[i];
+    for (int i = 0; i < 3; ++i) m.o[i] = c[i];
+    m.use_s2w = 1;
+}
+
+// The inverse of a pose E = [R | t]: Rt = R^T and o = -Rt t, each o[i] a left-to-right sum of three
+// double products rounded once (cv::gemm on CV_32F, tsdf.cu:432-435).  Two forms of o, equal but for
+// the sign of a zero when all three products are -0.0:
+//   cam_origin        (float)(-(0.0 + p0 + p1 + p2))  semtsdf_pose_camera, the ICP system: -0.0f there
+//   cam_origin_assoc  -(float)(p0 + p1 + p2)          the association march:               +0.0f there
+inline void cam_rt(float Rt[9], const float E[16]) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) Rt[i * 3 + j] = E[j * 4 + i];
+}
+inline void cam_origin(float o[3], const float E[16]) {
+    for (int i = 0; i < 3; ++i) {
+        double acc = 0;
+        for (int k = 0; k < 3; ++k) acc += (double)E[k * 4 + i] * (double)E[k * 4 + 3];
+        o[i] = (float)(-acc);
+    }
+}
+inline void cam_origin_assoc(float o[3], const float E[16]) {
+    for (int i = 0; i < 3; ++i)
+        o[i] = -(float)((double)E[i] * (double)E[3] + (double)E[4 + i] * (double)E[7] + (double)E[8 + i] * (double)E[11]);
+}
+
+// Bump carver of one staging allocation for n pixels: typed sub-arrays of per_px * n + fixed
+// elements in the order asked for, each at its natural alignment, and the bytes used so far.  A null
+// base only measures.  The layouts below carve in declaration order; their bytes is the total.
+struct Carver {
+    Carver(void* base, size_t n) : base(static_cast<char*>(base)), n(n) {}
+    char* base;
+    size_t n, bytes = 0;
+    template <class T>
+    T* take(size_t per_px, size_t fixed = 0) {
+        bytes = (bytes + alignof(T) - 1) / alignof(T) * alignof(T);
+        T* p = base ? reinterpret_cast<T*>(base + bytes) : nullptr;
+        bytes += (per_px * n + fixed) * sizeof(T);
+        return p;
+    }
+};
+
+// semtsdf_render_maps: the six maps, 34 B per pixel.
+struct MapsScratch {
+    Carver c;
+    float *t = c.take<float>(1), *point = c.take<float>(3), *normal = c.take<float>(3), *votes = c.take<float>(1);
+    uint8_t *label = c.take<uint8_t>(1), *flags = c.take<uint8_t>(1);
+    size_t bytes = c.bytes;
+};
+
+// semtsdf_frame_maps and semtsdf_icp_system: frame and model maps, the system's words, the two flag
+// maps and the depth image, 52 B per pixel + 8 B per word.
+struct TrackScratch {
+    Carver c;
+    size_t nwords;
+    float *vertex = c.take<float>(3), *normal = c.take<float>(3), *m_point = c.take<float>(3), *m_normal = c.take<float>(3);
+    int64_t* words = c.take<int64_t>(0, nwords);
+    uint8_t *flags = c.take<uint8_t>(1), *m_flags = c.take<uint8_t>(1);
+    uint16_t* depth = c.take<uint16_t>(1);
+    size_t bytes = c.bytes;
+};
+
+// The sharded ray protocol's per-pixel march state (ShardRayState), 24 B per pixel.
+struct RayScratch {
+    Carver c;
+    int* k = c.take<int>(1);
+    float* fk = c.take<float>(1);
+    int* j = c.take<int>(1);
+    float *fj = c.take<float>(1), *fp = c.take<float>(1), *t = c.take<float>(1);
+    size_t bytes = c.bytes;
+};
+
+}  // namespace semtsdf
+
