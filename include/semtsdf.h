@@ -394,6 +394,84 @@ int semtsdf_icp_system_dev(semtsdf_vol* v, const semtsdf_icp_in* in_dev, const f
                            const float E_cur[16], float dist_max, float cos_min, int32_t stride, int64_t* words_dev,
                            void* stream);
 
+/* ---- depth pyramid: coarse-to-fine tracking on filtered depth (no reference counterpart) -----------
+ * The frame side of coarse-to-fine ICP: an edge-preserving filter of the depth image (level 0), up to
+ * three band-limited halvings of it, the frame maps of every level, and the system of one iteration
+ * with a frame grid of its own.  All arithmetic is f32 and every operation is rounded on its own
+ * unless written fmaf; there is no exp, the weights are polynomials.  W, H, K, Kinv and depth_scale are
+ * the handle's; no call reads or modifies the volume.
+ *
+ * Level geometry.  Level 0 is W x H with Kinv the upper-left 3 x 3 of the handle's Kinv, copied as
+ * it is.  Level l has width W >> l and height H >> l (floor).  With fx = K[0], fy = K[5], cx = K[2],
+ * cy = K[6], its camera is formed in double: fx_l = fx / 2^l, fy_l = fy / 2^l, cx_l = (cx + 0.5) / 2^l -
+ * 0.5, cy_l likewise (pixel centres lie at integers; coarse pixel x covers the fine pixels 2x and
+ * 2x + 1), and Kinv_l = [[1 / fx_l, 0, -cx_l / fx_l], [0, 1 / fy_l, -cy_l / fy_l], [0, 0, 1]], each entry
+ * rounded once to f32.
+ *
+ * Level 0 depth.  zc = (float)D / depth_scale of raw depth D (the frame maps' value).  radius 0:
+ * z0 = zc.  radius R in 1..4: D == 0 gives z0 = +0 (holes are never filled).  Otherwise, with
+ * inv_s = 1.0f / (float)((R + 1)^2) and inv_r = 1.0f / sigma_r (IEEE divisions, formed before the
+ * launch), num = den = 0 and the neighbours (x + dx, y + dy) visited with dy = -R..R ascending, then
+ * dx = -R..R ascending: a neighbour off the image or with raw depth 0 is skipped; so is one with
+ * us = 1.0f - (float)(dx^2 + dy^2) * inv_s not > 0 (at R = 4 that leaves 69 of the 81 taps, at R = 3 45
+ * of 49); for the rest, zn the neighbour's (float)D / depth_scale: d = zn - zc, e = d * inv_r,
+ * u = 1.0f - e * e, skipped unless u > 0; w = (us * us) * (u * u) (three rounded products),
+ * num = fmaf(w, d, num), den = den + w.  z0 = zc + num / den (an IEEE division; the centre contributes
+ * w = 1, so den >= 1).  A neighbour further than sigma_r in depth has no weight, so a step larger than
+ * sigma_r is left exactly as it is, and a constant image comes back bit for bit.
+ *
+ * Halving.  Level l + 1 at (x, y), with b = z_l(2x, 2y): b == 0 gives +0.  Otherwise s = n = 0 and for
+ * q = z_l(2x, 2y), z_l(2x + 1, 2y), z_l(2x, 2y + 1), z_l(2x + 1, 2y + 1) in that order, each with q != 0 and
+ * fabsf(q - b) <= band: s = s + (q - b), n = n + 1.  z_{l+1} = b + s / (float)n.
+ *
+ * Maps of a level: the frame maps' rule (above) with the level's z in place of (float)D / depth_scale
+ * and the level's Kinv, width and height; flags bit 0 = (z != 0).  With radius 0, level 0 equals
+ * semtsdf_frame_maps in every bit.
+ *
+ * semtsdf_frame_level: width, height and Kinv are written by the library; z is required at every level,
+ * vertex, normal and flags may each be NULL; an output requested alone equals that of the full call.
+ * semtsdf_frame_levels: writes width, height and Kinv of nlevels levels and touches no device.
+ * semtsdf_frame_pyramid_dev: device pointers (depth_d and those in the structs, which stay host
+ *   memory); allocates nothing, only enqueues on the stream (the filter, nlevels - 1 halvings, one maps
+ *   launch per level with an output), reads nothing back.
+ * semtsdf_frame_pyramid: host pointers; synchronises.  Its device scratch (2 B per pixel and 29 B per
+ *   pixel of each of the four levels the image admits) is the handle's, counted in device_bytes and
+ *   kept after the first call; failing to get it is SEMTSDF_ERR_OOM and the handle stays usable.
+ * Errors, all decided before any device work: a NULL argument or a NULL z; nlevels outside
+ * 1..SEMTSDF_PYRAMID_MAX_LEVELS; a coarsest level narrower or lower than 2 pixels; nlevels > 1 with K[1]
+ * or K[4] nonzero; radius outside 0..4; radius > 0 with sigma_r not finite or <= 0; nlevels > 1 with
+ * band not finite or <= 0: SEMTSDF_ERR_INVALID.  A Z-sharded handle: SEMTSDF_ERR_UNSUPPORTED.
+ *
+ * semtsdf_icp_system_level: semtsdf_icp_system with two pixel grids.  The visited pixels, stride and
+ * the row pitch of the frame maps come from frame_width x frame_height; Pw is projected, bounded and
+ * looked up in the model maps with the handle's K, W and H: the model maps stay the one
+ * full-resolution render of the reference view, and a coarse frame pixel finds a true model point
+ * and normal, which is all that projective association asks for.  Steps, words and errors are
+ * semtsdf_icp_system's, with frame_width, frame_height >= 1 and frame_width * frame_height <= 2^19 in
+ * place of its bound on W * H (the host variant also needs frame_width * frame_height <= W * H: it
+ * shares semtsdf_icp_system's scratch).  With frame_width = W and frame_height = H the words are
+ * semtsdf_icp_system's. */
+#define SEMTSDF_PYRAMID_MAX_LEVELS 4
+typedef struct semtsdf_frame_level {
+    int32_t width, height; /* written by the library */
+    float Kinv[9];         /* written: row-major 3x3 of the level */
+    float* z;              /* [h*w] metres, 0 = no depth; required at every level */
+    float* vertex;         /* [h*w*3] optional */
+    float* normal;         /* [h*w*3] optional */
+    uint8_t* flags;        /* [h*w]   optional */
+} semtsdf_frame_level;
+int semtsdf_frame_levels(const semtsdf_vol* v, int nlevels, semtsdf_frame_level* levels);
+int semtsdf_frame_pyramid(semtsdf_vol* v, const uint16_t* depth, int radius, float sigma_r, float band, int nlevels,
+                          semtsdf_frame_level* levels_host, void* stream);
+int semtsdf_frame_pyramid_dev(semtsdf_vol* v, const uint16_t* depth_d, int radius, float sigma_r, float band,
+                              int nlevels, semtsdf_frame_level* levels_dev, void* stream);
+int semtsdf_icp_system_level(semtsdf_vol* v, const semtsdf_icp_in* in_host, int32_t frame_width, int32_t frame_height,
+                             const float E_ref[16], const float E_cur[16], float dist_max, float cos_min,
+                             int32_t stride, int64_t* words_host, void* stream);
+int semtsdf_icp_system_level_dev(semtsdf_vol* v, const semtsdf_icp_in* in_dev, int32_t frame_width,
+                                 int32_t frame_height, const float E_ref[16], const float E_cur[16], float dist_max,
+                                 float cos_min, int32_t stride, int64_t* words_dev, void* stream);
+
 /* ---- Z-sharded raycast (replaces the single-GPU back_proj_kernel
  * tsdf.cu:72-135 and show_tsdf_kernel viewer.cu:17-86 when the volume is split across GPUs)
  * Every shard of a group runs the same call sequence.  Between calls the host exchanges

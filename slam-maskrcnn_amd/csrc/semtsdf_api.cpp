@@ -143,6 +143,7 @@ struct semtsdf_vol {
     float* render_t_d = nullptr;
     uint8_t* maps_d = nullptr;     // semtsdf_render_maps: the six maps back to back (34 B per pixel)
     uint8_t* track_d = nullptr;    // semtsdf_frame_maps / semtsdf_icp_system: host-variant scratch (52 B per pixel)
+    uint8_t* pyramid_d = nullptr;  // semtsdf_frame_pyramid: host-variant scratch (PyramidScratch)
     unsigned long long* counters_d = nullptr;
     IntegrateRare* rare_d = nullptr;  // the integrate's rare-path fields (IntegrateArgs::rare)
     float* rcp_table_d = nullptr;    // RN(1/n), n = 1..kRcpTable
@@ -1904,15 +1905,15 @@ int semtsdf_frame_maps(semtsdf_vol* v, const uint16_t* depth, float* vertex, flo
     return copies_out(s, {{vertex, t.vertex, n * 12}, {normal, t.normal, n * 12}, {flags, t.flags, n}});
 }
 
-// Argument checks of the system, all before any device work.
-static int icp_check(semtsdf_vol* v, const semtsdf_icp_in* in, const float* E_ref, const float* E_cur, float dist_max,
-                     float cos_min, int32_t stride, const int64_t* words) {
+// Argument checks of the system, all before any device work.  fw x fh: the frame maps' grid.
+static int icp_check(semtsdf_vol* v, const semtsdf_icp_in* in, int32_t fw, int32_t fh, const float* E_ref,
+                     const float* E_cur, float dist_max, float cos_min, int32_t stride, const int64_t* words) {
     if (!v || !in || !E_ref || !E_cur || !words) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
     if (!in->vertex || !in->normal || !in->flags || !in->m_point || !in->m_normal || !in->m_flags)
         return fail(SEMTSDF_ERR_INVALID, "NULL input map");
-    if (npx(v) > ((size_t)1 << 19))
+    if (fw < 1 || fh < 1 || (size_t)fw * (size_t)fh > ((size_t)1 << 19))
         return fail(SEMTSDF_ERR_INVALID, "image %d x %d has more than 2^19 pixels (the bound of the integer sums)",
-                    v->p.width, v->p.height);
+                    (int)fw, (int)fh);
     if (stride < 1) return fail(SEMTSDF_ERR_INVALID, "stride=%d must be >= 1", (int)stride);
     if (!(dist_max > 0.0f && dist_max <= 1.0f))
         return fail(SEMTSDF_ERR_INVALID, "dist_max=%g outside (0, 1]", (double)dist_max);
@@ -1923,8 +1924,9 @@ static int icp_check(semtsdf_vol* v, const semtsdf_icp_in* in, const float* E_re
     return SEMTSDF_OK;
 }
 
-static int icp_impl(semtsdf_vol* v, const semtsdf_icp_in& in_d, const float E_ref[16], const float E_cur[16],
-                    float dist_max, float cos_min, int32_t stride, int64_t* words_d, hipStream_t s) {
+static int icp_impl(semtsdf_vol* v, const semtsdf_icp_in& in_d, int32_t fw, int32_t fh, const float E_ref[16],
+                    const float E_cur[16], float dist_max, float cos_min, int32_t stride, int64_t* words_d,
+                    hipStream_t s) {
     IcpArgs a{};
     a.vertex = in_d.vertex; a.normal = in_d.normal; a.flags = in_d.flags;
     a.m_point = in_d.m_point; a.m_normal = in_d.m_normal; a.m_flags = in_d.m_flags;
@@ -1934,36 +1936,179 @@ static int icp_impl(semtsdf_vol* v, const semtsdf_icp_in& in_d, const float E_re
     fill_E(a.Eref, E_ref);
     a.dmax2 = dist_max * dist_max; a.cos_min = cos_min; a.stride = stride;
     a.width = v->p.width; a.height = v->p.height;
+    a.fwidth = fw; a.fheight = fh;
     a.words = reinterpret_cast<long long*>(words_d);
     HIPC(hipMemsetAsync(words_d, 0, kIcpWords * 8, s));
     HIPC(launch_icp_system(a, s));
     return SEMTSDF_OK;
 }
 
+int semtsdf_icp_system_level_dev(semtsdf_vol* v, const semtsdf_icp_in* in_dev, int32_t frame_width,
+                                 int32_t frame_height, const float E_ref[16], const float E_cur[16], float dist_max,
+                                 float cos_min, int32_t stride, int64_t* words_dev, void* stream) {
+    if (int rc = icp_check(v, in_dev, frame_width, frame_height, E_ref, E_cur, dist_max, cos_min, stride, words_dev))
+        return rc;
+    HIPC(hipSetDevice(v->device));
+    return icp_impl(v, *in_dev, frame_width, frame_height, E_ref, E_cur, dist_max, cos_min, stride, words_dev,
+                    pick(v, stream));
+}
+
+int semtsdf_icp_system_level(semtsdf_vol* v, const semtsdf_icp_in* in_host, int32_t frame_width, int32_t frame_height,
+                             const float E_ref[16], const float E_cur[16], float dist_max, float cos_min,
+                             int32_t stride, int64_t* words_host, void* stream) {
+    if (int rc = icp_check(v, in_host, frame_width, frame_height, E_ref, E_cur, dist_max, cos_min, stride, words_host))
+        return rc;
+    const size_t n = npx(v), nf = (size_t)frame_width * (size_t)frame_height;  // model and frame pixels
+    if (nf > n)
+        return fail(SEMTSDF_ERR_INVALID, "frame maps %d x %d larger than the handle's image (the host variant's scratch)",
+                    (int)frame_width, (int)frame_height);
+    HIPC(hipSetDevice(v->device));
+    hipStream_t s = pick(v, stream);
+    if (int rc = track_scratch(v)) return rc;
+    const TrackScratch t{{v->track_d, n}, kIcpWords};
+    const semtsdf_icp_in& h = *in_host;
+    if (int rc = queue_copies(s, hipMemcpyHostToDevice, {{t.vertex, h.vertex, nf * 12}, {t.normal, h.normal, nf * 12},
+                                                         {t.m_point, h.m_point, n * 12}, {t.m_normal, h.m_normal, n * 12},
+                                                         {t.flags, h.flags, nf}, {t.m_flags, h.m_flags, n}}))
+        return rc;
+    semtsdf_icp_in d{t.vertex, t.normal, t.flags, t.m_point, t.m_normal, t.m_flags};
+    if (int rc = icp_impl(v, d, frame_width, frame_height, E_ref, E_cur, dist_max, cos_min, stride, t.words, s))
+        return rc;
+    return copies_out(s, {{words_host, t.words, kIcpWords * 8}});
+}
+
+// The system on the handle's own grid: the level variant with the frame at W x H.
 int semtsdf_icp_system_dev(semtsdf_vol* v, const semtsdf_icp_in* in_dev, const float E_ref[16],
                            const float E_cur[16], float dist_max, float cos_min, int32_t stride, int64_t* words_dev,
                            void* stream) {
-    if (int rc = icp_check(v, in_dev, E_ref, E_cur, dist_max, cos_min, stride, words_dev)) return rc;
-    HIPC(hipSetDevice(v->device));
-    return icp_impl(v, *in_dev, E_ref, E_cur, dist_max, cos_min, stride, words_dev, pick(v, stream));
+    if (!v) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
+    return semtsdf_icp_system_level_dev(v, in_dev, v->p.width, v->p.height, E_ref, E_cur, dist_max, cos_min, stride,
+                                        words_dev, stream);
 }
 
 int semtsdf_icp_system(semtsdf_vol* v, const semtsdf_icp_in* in_host, const float E_ref[16], const float E_cur[16],
                        float dist_max, float cos_min, int32_t stride, int64_t* words_host, void* stream) {
-    if (int rc = icp_check(v, in_host, E_ref, E_cur, dist_max, cos_min, stride, words_host)) return rc;
+    if (!v) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
+    return semtsdf_icp_system_level(v, in_host, v->p.width, v->p.height, E_ref, E_cur, dist_max, cos_min, stride,
+                                    words_host, stream);
+}
+
+// ---- depth pyramid: filtered level 0, halvings, the maps of every level -------------------------
+// Argument checks of the three pyramid calls, all before any device work; compute: the two that launch
+// (semtsdf_frame_levels has no depth, filter or outputs to check).
+static int pyramid_check(const semtsdf_vol* v, const void* depth, int radius, float sigma_r, float band, int nlevels,
+                         const semtsdf_frame_level* levels, bool compute) {
+    if (!v || !levels || (compute && !depth)) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
+    if (nlevels < 1 || nlevels > kPyramidMaxLevels)
+        return fail(SEMTSDF_ERR_INVALID, "nlevels=%d outside 1..%d", nlevels, kPyramidMaxLevels);
+    if ((v->p.width >> (nlevels - 1)) < 2 || (v->p.height >> (nlevels - 1)) < 2)
+        return fail(SEMTSDF_ERR_INVALID, "level %d of a %d x %d image is narrower or lower than 2 pixels", nlevels - 1,
+                    v->p.width, v->p.height);
+    if (nlevels > 1 && (v->p.K[1] != 0.0f || v->p.K[4] != 0.0f))
+        return fail(SEMTSDF_ERR_INVALID, "a pyramid needs K[1] = K[4] = 0 (no skew)");
+    if (compute) {
+        for (int l = 0; l < nlevels; ++l)
+            if (!levels[l].z) return fail(SEMTSDF_ERR_INVALID, "NULL z of level %d", l);
+        if (radius < 0 || radius > kFilterMaxRadius)
+            return fail(SEMTSDF_ERR_INVALID, "radius=%d outside 0..%d", radius, kFilterMaxRadius);
+        if (radius > 0 && !(std::isfinite(sigma_r) && sigma_r > 0.0f))
+            return fail(SEMTSDF_ERR_INVALID, "sigma_r=%g must be finite and > 0", (double)sigma_r);
+        if (nlevels > 1 && !(std::isfinite(band) && band > 0.0f))
+            return fail(SEMTSDF_ERR_INVALID, "band=%g must be finite and > 0", (double)band);
+    }
+    if (v->p.z_nshards != 1)
+        return fail(SEMTSDF_ERR_UNSUPPORTED, "the depth pyramid on a Z-sharded handle is not supported");
+    return SEMTSDF_OK;
+}
+
+static void pyramid_geometry(const semtsdf_vol* v, int nlevels, semtsdf_frame_level* levels) {
+    for (int l = 0; l < nlevels; ++l) {
+        levels[l].width = v->p.width >> l;
+        levels[l].height = v->p.height >> l;
+        if (l == 0)
+            cam_mat3(levels[l].Kinv, v->p.Kinv);
+        else
+            cam_level_kinv(levels[l].Kinv, v->p.K, l);
+    }
+}
+
+int semtsdf_frame_levels(const semtsdf_vol* v, int nlevels, semtsdf_frame_level* levels) {
+    if (int rc = pyramid_check(v, nullptr, 0, 0.0f, 0.0f, nlevels, levels, false)) return rc;
+    pyramid_geometry(v, nlevels, levels);
+    return SEMTSDF_OK;
+}
+
+// The launches of one pyramid on device pointers: the filter, the halvings, the maps of every level
+// with an output.  lv: geometry filled in.
+static int pyramid_impl(semtsdf_vol* v, const uint16_t* depth_d, int radius, float sigma_r, float band, int nlevels,
+                        const semtsdf_frame_level* lv, hipStream_t s) {
+    DepthFilterArgs f{};
+    f.depth = depth_d;
+    f.depth_scale = v->p.depth_scale;
+    f.inv_r = radius > 0 ? 1.0f / sigma_r : 0.0f;
+    f.radius = radius;
+    f.width = lv[0].width; f.height = lv[0].height;
+    f.z = lv[0].z;
+    HIPC(launch_depth_filter(f, s));
+    for (int l = 1; l < nlevels; ++l) {
+        DepthHalveArgs h{};
+        h.src = lv[l - 1].z;
+        h.width = lv[l - 1].width; h.height = lv[l - 1].height;
+        h.band = band;
+        h.dst = lv[l].z;
+        HIPC(launch_depth_halve(h, s));
+    }
+    for (int l = 0; l < nlevels; ++l) {
+        if (!lv[l].vertex && !lv[l].normal && !lv[l].flags) continue;
+        FrameMapsArgs a{};
+        a.z = lv[l].z;
+        for (int i = 0; i < 9; ++i) a.Kinv[i] = lv[l].Kinv[i];
+        a.depth_scale = v->p.depth_scale;
+        a.width = lv[l].width; a.height = lv[l].height;
+        a.vertex = lv[l].vertex; a.normal = lv[l].normal; a.flags = lv[l].flags;
+        HIPC(launch_frame_maps(a, s));
+    }
+    return SEMTSDF_OK;
+}
+
+int semtsdf_frame_pyramid_dev(semtsdf_vol* v, const uint16_t* depth_d, int radius, float sigma_r, float band,
+                              int nlevels, semtsdf_frame_level* levels_dev, void* stream) {
+    if (int rc = pyramid_check(v, depth_d, radius, sigma_r, band, nlevels, levels_dev, true)) return rc;
+    pyramid_geometry(v, nlevels, levels_dev);
+    HIPC(hipSetDevice(v->device));
+    return pyramid_impl(v, depth_d, radius, sigma_r, band, nlevels, levels_dev, pick(v, stream));
+}
+
+int semtsdf_frame_pyramid(semtsdf_vol* v, const uint16_t* depth, int radius, float sigma_r, float band, int nlevels,
+                          semtsdf_frame_level* levels_host, void* stream) {
+    if (int rc = pyramid_check(v, depth, radius, sigma_r, band, nlevels, levels_host, true)) return rc;
+    pyramid_geometry(v, nlevels, levels_host);
     HIPC(hipSetDevice(v->device));
     hipStream_t s = pick(v, stream);
-    const size_t n = npx(v);
-    if (int rc = track_scratch(v)) return rc;
-    const TrackScratch t{{v->track_d, n}, kIcpWords};
-    const semtsdf_icp_in& h = *in_host;
-    if (int rc = queue_copies(s, hipMemcpyHostToDevice, {{t.vertex, h.vertex, n * 12}, {t.normal, h.normal, n * 12},
-                                                         {t.m_point, h.m_point, n * 12}, {t.m_normal, h.m_normal, n * 12},
-                                                         {t.flags, h.flags, n}, {t.m_flags, h.m_flags, n}}))
+    if (int rc = v->pyramid_d ? 0
+                              : v->pool.alloc((void**)&v->pyramid_d,
+                                              PyramidScratch(nullptr, v->p.width, v->p.height).bytes))
         return rc;
-    semtsdf_icp_in d{t.vertex, t.normal, t.flags, t.m_point, t.m_normal, t.m_flags};
-    if (int rc = icp_impl(v, d, E_ref, E_cur, dist_max, cos_min, stride, t.words, s)) return rc;
-    return copies_out(s, {{words_host, t.words, kIcpWords * 8}});
+    const PyramidScratch t(v->pyramid_d, v->p.width, v->p.height);
+    semtsdf_frame_level d[kPyramidMaxLevels];
+    for (int l = 0; l < nlevels; ++l) {
+        const semtsdf_frame_level& h = levels_host[l];
+        d[l] = h;
+        d[l].z = t.z[l];
+        d[l].vertex = h.vertex ? t.vertex[l] : nullptr;
+        d[l].normal = h.normal ? t.normal[l] : nullptr;
+        d[l].flags = h.flags ? t.flags[l] : nullptr;
+    }
+    if (int rc = queue_copies(s, hipMemcpyHostToDevice, {{t.depth, depth, npx(v) * 2}})) return rc;
+    if (int rc = pyramid_impl(v, t.depth, radius, sigma_r, band, nlevels, d, s)) return rc;
+    for (int l = 0; l < nlevels; ++l) {
+        const semtsdf_frame_level& h = levels_host[l];
+        const size_t n = (size_t)h.width * (size_t)h.height;
+        if (int rc = queue_copies(s, hipMemcpyDeviceToHost, {{h.z, d[l].z, n * 4}, {h.vertex, d[l].vertex, n * 12},
+                                                             {h.normal, d[l].normal, n * 12}, {h.flags, d[l].flags, n}}))
+            return rc;
+    }
+    return copies_out(s, {});
 }
 
 // Voxels of the reference layout (rows of lz planes) held by the handle.

@@ -78,6 +78,38 @@ struct TrackScratch {
     size_t bytes = c.bytes;
 };
 
+// The inverse camera matrix of pyramid level l >= 1 (row-major 3x3) from the 4x4 K of level 0: the
+// focal lengths halve per level and a coarse pixel covers the fine pixels 2x and 2x + 1 (pixel centres
+// at integers), so c_l = (c + 0.5) / 2^l - 0.5.  Formed in double, each entry rounded once.
+inline void cam_level_kinv(float dst[9], const float K[16], int level) {
+    const double s = (double)(1 << level);
+    const double fx = (double)K[0] / s, fy = (double)K[5] / s;
+    const double cx = ((double)K[2] + 0.5) / s - 0.5, cy = ((double)K[6] + 0.5) / s - 0.5;
+    const double m[9] = {1.0 / fx, 0.0, -cx / fx, 0.0, 1.0 / fy, -cy / fy, 0.0, 0.0, 1.0};
+    for (int i = 0; i < 9; ++i) dst[i] = (float)m[i];
+}
+
+// semtsdf_frame_pyramid: z and the three maps of every level the image admits (29 B per pixel of a
+// level, at most kLevels of them) and the depth image.
+struct PyramidScratch {
+    static constexpr int kLevels = 4;  // SEMTSDF_PYRAMID_MAX_LEVELS
+    Carver c;
+    float *z[kLevels], *vertex[kLevels], *normal[kLevels];
+    uint8_t* flags[kLevels];
+    uint16_t* depth;
+    size_t bytes;
+    PyramidScratch(void* base, int width, int height) : c(base, 0) {
+        size_t n[kLevels];
+        for (int l = 0; l < kLevels; ++l) n[l] = (size_t)(width >> l) * (size_t)(height >> l);
+        for (int l = 0; l < kLevels; ++l) z[l] = c.take<float>(0, n[l]);
+        for (int l = 0; l < kLevels; ++l) vertex[l] = c.take<float>(0, 3 * n[l]);
+        for (int l = 0; l < kLevels; ++l) normal[l] = c.take<float>(0, 3 * n[l]);
+        depth = c.take<uint16_t>(0, n[0]);
+        for (int l = 0; l < kLevels; ++l) flags[l] = c.take<uint8_t>(0, n[l]);
+        bytes = c.bytes;
+    }
+};
+
 // The sharded ray protocol's per-pixel march state (ShardRayState), 24 B per pixel.
 struct RayScratch {
     Carver c;

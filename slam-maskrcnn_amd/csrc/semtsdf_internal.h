@@ -300,8 +300,10 @@ struct MapsArgs {
 };
 
 // Frame maps of a depth image (k_frame_maps): camera-space vertex, normal, validity byte, each nullable.
+// The depth of a pixel is (float)depth / depth_scale, or z itself for a pyramid level (depth null).
 struct FrameMapsArgs {
     const uint16_t* depth;  // [npx]
+    const float* z;         // [npx] metres, 0 = no depth (k_frame_maps<true>)
     float Kinv[9];
     float depth_scale;
     int width, height;
@@ -325,8 +327,29 @@ struct IcpArgs {
     float K[9];
     float dmax2, cos_min;
     int stride;
-    int width, height;
+    int width, height;      // the model maps' grid (the handle's): projection bounds and row pitch
+    int fwidth, fheight;    // the frame maps' grid: visited pixels and row pitch
     long long* words;       // [kIcpWords], zeroed before the launch
+};
+
+// Level 0 of the depth pyramid (k_depth_filter): the edge-preserving filter of include/semtsdf.h.
+constexpr int kPyramidMaxLevels = 4;   // SEMTSDF_PYRAMID_MAX_LEVELS
+constexpr int kFilterMaxRadius = 4;
+struct DepthFilterArgs {
+    const uint16_t* depth;  // [npx]
+    float depth_scale;
+    float inv_r;            // 1 / sigma_r, formed on the host
+    int radius;             // 0..kFilterMaxRadius
+    int width, height;
+    float* z;               // [npx]
+};
+
+// One halving of the pyramid (k_depth_halve): level l (w x h) -> level l + 1 ((w >> 1) x (h >> 1)).
+struct DepthHalveArgs {
+    const float* src;       // [h][w]
+    int width, height;      // of src
+    float band;
+    float* dst;             // [h >> 1][w >> 1]
 };
 
 // Z-sharded raycast protocol (k_shard_* in semtsdf_kernels.hip): per-pixel march state.
@@ -415,6 +438,8 @@ hipError_t launch_render(const RenderArgs& a, hipStream_t s);
 hipError_t launch_model_maps(const MapsArgs& a, hipStream_t s);
 hipError_t launch_frame_maps(const FrameMapsArgs& a, hipStream_t s);
 hipError_t launch_icp_system(const IcpArgs& a, hipStream_t s);
+hipError_t launch_depth_filter(const DepthFilterArgs& a, hipStream_t s);
+hipError_t launch_depth_halve(const DepthHalveArgs& a, hipStream_t s);
 hipError_t launch_march_fused(const AssocArgs& aa, const RenderArgs& ra, hipStream_t s);
 hipError_t launch_copy_host(const void* src, void* dst, size_t n16, hipStream_t s);
 // chunk [v0, v0+nv) of the bin-major histogram <-> voxel-major [nv][32] staging buffer

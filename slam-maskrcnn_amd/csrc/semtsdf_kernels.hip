@@ -3612,32 +3612,48 @@ __device__ __forceinline__ void cross3(const float a[3], const float b[3], float
     out[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-// V = (Kinv (x, y, 1)) * (d / depth_scale) of a pixel with nonzero raw depth d
-__device__ __forceinline__ void frame_vertex(const FrameMapsArgs& a, int x, int y, unsigned d, float V[3]) {
-    const float z = (float)d / a.depth_scale;
+// The depth of pixel px in metres and whether it has one: (float)D / depth_scale and D != 0 of the raw
+// image, or the stored value of a pyramid level and z != 0 (kZ).
+template <bool kZ>
+__device__ __forceinline__ bool frame_depth(const FrameMapsArgs& a, size_t px, float& z) {
+    if constexpr (kZ) {
+        z = a.z[px];
+        return z != 0.0f;
+    } else {
+        const unsigned d = a.depth[px];
+        z = (float)d / a.depth_scale;
+        return d != 0;
+    }
+}
+
+// V = (Kinv (x, y, 1)) * z of a pixel with depth z
+__device__ __forceinline__ void frame_vertex(const FrameMapsArgs& a, int x, int y, float z, float V[3]) {
     const float fx = (float)x, fy = (float)y;
     V[0] = dot3(a.Kinv[0], a.Kinv[1], a.Kinv[2], fx, fy, 1.0f) * z;
     V[1] = dot3(a.Kinv[3], a.Kinv[4], a.Kinv[5], fx, fy, 1.0f) * z;
     V[2] = dot3(a.Kinv[6], a.Kinv[7], a.Kinv[8], fx, fy, 1.0f) * z;
 }
 
+// kZ: the maps of a pyramid level, from its z and its own Kinv, width and height.
+template <bool kZ>
 __global__ __launch_bounds__(256) void k_frame_maps(FrameMapsArgs a) {
     const int x = (int)blockIdx.x * 16 + (int)(threadIdx.x & 15);
     const int y = (int)blockIdx.y * 16 + (int)(threadIdx.x >> 4);
     if (x >= a.width || y >= a.height) return;
     const size_t px = (size_t)y * a.width + x;
-    const unsigned d = a.depth[px];
+    float z;
     float V[3] = {0.0f, 0.0f, 0.0f}, n[3] = {0.0f, 0.0f, 0.0f};
     unsigned fl = 0;
-    if (d) {
+    if (frame_depth<kZ>(a, px, z)) {
         fl = 1u;
-        frame_vertex(a, x, y, d, V);
+        frame_vertex(a, x, y, z, V);
         if ((a.normal || a.flags) && x + 1 < a.width && y + 1 < a.height) {
-            const unsigned dr = a.depth[px + 1], dd = a.depth[px + (size_t)a.width];
-            if (dr && dd) {
+            float zr, zd;
+            const bool hr = frame_depth<kZ>(a, px + 1, zr), hd = frame_depth<kZ>(a, px + (size_t)a.width, zd);
+            if (hr && hd) {
                 float A[3], B[3], g[3];
-                frame_vertex(a, x, y + 1, dd, A);
-                frame_vertex(a, x + 1, y, dr, B);
+                frame_vertex(a, x, y + 1, zd, A);
+                frame_vertex(a, x + 1, y, zr, B);
                 for (int k = 0; k < 3; ++k) {
                     A[k] -= V[k];
                     B[k] -= V[k];
@@ -3669,7 +3685,147 @@ __global__ __launch_bounds__(256) void k_frame_maps(FrameMapsArgs a) {
 
 hipError_t launch_frame_maps(const FrameMapsArgs& a, hipStream_t s) {
     const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-    hipLaunchKernelGGL(k_frame_maps, grid, dim3(256), 0, s, a);
+    if (a.z)
+        hipLaunchKernelGGL(k_frame_maps<true>, grid, dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL(k_frame_maps<false>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// depth pyramid (include/semtsdf.h, "depth pyramid"): level 0 is the raw depth in metres through an
+// edge-preserving filter with polynomial weights, each further level one band-limited 2 x 2 mean.
+// ------------------------------------------------------------------------------------
+constexpr int kFilterTile = 16;
+constexpr int kFilterPitch = 48;  // >= 16 + 2 * kFilterMaxRadius and = 16 mod 32: the two 16-pixel rows of a
+                                  // 32-lane ds_read_b32 group fall on disjoint banks
+static_assert(kFilterPitch >= kFilterTile + 2 * kFilterMaxRadius && kFilterPitch % 32 == 16, "filter tile pitch");
+
+// us * us of every tap's spatial term us = 1 - (float)(dx^2 + dy^2) * inv_s with inv_s = 1.0f / (float)((R + 1)^2),
+// 0 where us <= 0 (no tap): constants of R, evaluated by the compiler with IEEE rounding of each
+// operation (the values the host would form), so the unrolled taps carry them as literals.
+template <int R>
+struct FilterTaps {
+    float w[2 * R + 1][2 * R + 1];
+    int count = 0;
+    constexpr FilterTaps() : w{} {
+        const float inv_s = 1.0f / (float)((R + 1) * (R + 1));
+        for (int dy = -R; dy <= R; ++dy)
+            for (int dx = -R; dx <= R; ++dx) {
+                const float m = (float)(dx * dx + dy * dy) * inv_s;
+                const float us = 1.0f - m;
+                w[dy + R][dx + R] = us > 0.0f ? us * us : 0.0f;
+                count += us > 0.0f;
+            }
+    }
+};
+static_assert(FilterTaps<1>().count == 9 && FilterTaps<2>().count == 25 && FilterTaps<3>().count == 45 &&
+                  FilterTaps<4>().count == 69, "taps of the spatial term");
+
+// One thread per pixel of a 16 x 16 tile.  The tile and its halo of R pixels are converted once into
+// LDS (0 off the image, which reads as "no depth"); the taps are unrolled with their spatial weights
+// as literals, so a tap is one LDS read and the range term.  A tap without depth or outside the
+// range adds w = +0, which leaves num and den as they are: the rule's "skip".
+template <int R>
+__global__ __launch_bounds__(256) void k_depth_filter(DepthFilterArgs a) {
+    constexpr int T = kFilterTile + 2 * R;
+    constexpr FilterTaps<R> taps;
+    __shared__ float tile[(kFilterTile + 2 * kFilterMaxRadius) * kFilterPitch];
+    const int tid = (int)threadIdx.x;
+    const int x0 = (int)blockIdx.x * kFilterTile - R, y0 = (int)blockIdx.y * kFilterTile - R;
+    for (int i = tid; i < T * T; i += 256) {
+        const int ty = i / T, tx = i - ty * T;
+        const int gx = x0 + tx, gy = y0 + ty;
+        float z = 0.0f;
+        if (gx >= 0 && gx < a.width && gy >= 0 && gy < a.height)
+            z = (float)a.depth[(size_t)gy * a.width + gx] / a.depth_scale;
+        tile[ty * kFilterPitch + tx] = z;
+    }
+    __syncthreads();
+    const int lx = tid & 15, ly = tid >> 4;
+    const int x = x0 + R + lx, y = y0 + R + ly;
+    if (x >= a.width || y >= a.height) return;
+    const float* c = tile + (ly + R) * kFilterPitch + (lx + R);
+    const float zc = c[0];
+    float out = zc;
+    if (zc != 0.0f) {
+        float num = 0.0f, den = 0.0f;
+#pragma unroll
+        for (int dy = -R; dy <= R; ++dy) {
+#pragma unroll
+            for (int dx = -R; dx <= R; ++dx) {
+                const float ws = taps.w[dy + R][dx + R];  // a literal of the unrolled body
+                if (ws == 0.0f) continue;
+                if (dx == 0 && dy == 0) {   // the centre: d = 0, u = 1, w = 1
+                    den = den + 1.0f;
+                    continue;
+                }
+                const float zn = c[dy * kFilterPitch + dx];
+                const float d = zn - zc;
+                const float e = d * a.inv_r;
+                const float u = 1.0f - e * e;
+                const float w = (zn != 0.0f && u > 0.0f) ? ws * (u * u) : 0.0f;
+                num = fmaf(w, d, num);
+                den = den + w;
+            }
+        }
+        out = zc + num / den;
+    }
+    a.z[(size_t)y * a.width + x] = out;
+}
+
+// radius 0: level 0 is the raw depth in metres, the frame maps' value.
+__global__ __launch_bounds__(256) void k_depth_metres(DepthFilterArgs a) {
+    const int x = (int)blockIdx.x * kFilterTile + (int)(threadIdx.x & 15);
+    const int y = (int)blockIdx.y * kFilterTile + (int)(threadIdx.x >> 4);
+    if (x >= a.width || y >= a.height) return;
+    const size_t px = (size_t)y * a.width + x;
+    a.z[px] = (float)a.depth[px] / a.depth_scale;
+}
+
+hipError_t launch_depth_filter(const DepthFilterArgs& a, hipStream_t s) {
+    const dim3 grid((a.width + kFilterTile - 1) / kFilterTile, (a.height + kFilterTile - 1) / kFilterTile);
+    switch (a.radius) {
+        case 0: hipLaunchKernelGGL(k_depth_metres, grid, dim3(256), 0, s, a); break;
+        case 1: hipLaunchKernelGGL(k_depth_filter<1>, grid, dim3(256), 0, s, a); break;
+        case 2: hipLaunchKernelGGL(k_depth_filter<2>, grid, dim3(256), 0, s, a); break;
+        case 3: hipLaunchKernelGGL(k_depth_filter<3>, grid, dim3(256), 0, s, a); break;
+        case 4: hipLaunchKernelGGL(k_depth_filter<4>, grid, dim3(256), 0, s, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// One thread per pixel of the coarser level: the mean of those of its 2 x 2 fine pixels that have depth
+// and lie within band of the first one, taken as offsets from it.  (w >> 1, h >> 1) by floor, so
+// 2x + 1 < w and 2y + 1 < h for every coarse pixel.
+__global__ __launch_bounds__(256) void k_depth_halve(DepthHalveArgs a) {
+    const int w = a.width >> 1, h = a.height >> 1;
+    const int x = (int)blockIdx.x * 16 + (int)(threadIdx.x & 15);
+    const int y = (int)blockIdx.y * 16 + (int)(threadIdx.x >> 4);
+    if (x >= w || y >= h) return;
+    const float* p = a.src + (size_t)(2 * y) * a.width + 2 * x;
+    const float q[4] = {p[0], p[1], p[a.width], p[a.width + 1]};
+    const float b = q[0];
+    float out = 0.0f;
+    if (b != 0.0f) {
+        float sum = 0.0f, n = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float d = q[k] - b;
+            if (q[k] != 0.0f && fabsf(d) <= a.band) {
+                sum += d;
+                n += 1.0f;
+            }
+        }
+        out = b + sum / n;
+    }
+    a.dst[(size_t)y * w + x] = out;
+}
+
+hipError_t launch_depth_halve(const DepthHalveArgs& a, hipStream_t s) {
+    const dim3 grid(((a.width >> 1) + 15) / 16, ((a.height >> 1) + 15) / 16);
+    hipLaunchKernelGGL(k_depth_halve, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -3692,8 +3848,8 @@ __global__ __launch_bounds__(256) void k_icp_system(IcpArgs a) {
     const long long yl = ((long long)blockIdx.y * 16 + (tid >> 4)) * a.stride;
     int cls = -1;  // 0 inlier, 1 far, 2 angle, 3 none; -1: not visited
     float J[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, r = 0.0f;
-    if (xl < a.width && yl < a.height) {
-        const size_t px = (size_t)yl * a.width + (size_t)xl;
+    if (xl < a.fwidth && yl < a.fheight) {  // the frame's grid; the model's (width, height) bounds the projection
+        const size_t px = (size_t)yl * a.fwidth + (size_t)xl;
         if ((a.flags[px] & 3u) == 3u) {
             cls = 3;
             const float V0 = a.vertex[px * 3 + 0], V1 = a.vertex[px * 3 + 1], V2 = a.vertex[px * 3 + 2];
@@ -3780,7 +3936,7 @@ __global__ __launch_bounds__(256) void k_icp_system(IcpArgs a) {
 }
 
 hipError_t launch_icp_system(const IcpArgs& a, hipStream_t s) {
-    const int nx = (a.width - 1) / a.stride + 1, ny = (a.height - 1) / a.stride + 1;  // visited pixels
+    const int nx = (a.fwidth - 1) / a.stride + 1, ny = (a.fheight - 1) / a.stride + 1;  // visited pixels
     const dim3 grid((nx + 15) / 16, (ny + 15) / 16);
     hipLaunchKernelGGL(k_icp_system, grid, dim3(256), 0, s, a);
     return hipGetLastError();

@@ -128,6 +128,13 @@ class IcpIn(C.Structure):
                 ("m_normal", C.c_void_p), ("m_flags", C.c_void_p)]
 
 
+class FrameLevel(C.Structure):
+    """semtsdf_frame_level: width, height and Kinv are written by the library; z is required."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("Kinv", C.c_float * 9), ("z", C.c_void_p),
+                ("vertex", C.c_void_p), ("normal", C.c_void_p), ("flags", C.c_void_p)]
+
+
+PYRAMID_MAX_LEVELS = 4
 ICP_WORDS = 32
 MAP_HIT = 0x1
 MAP_NORMAL = 0x2
@@ -208,6 +215,12 @@ SIGNATURES = {
     "semtsdf_frame_maps_dev": (_I, [_P, _P, _P, _P, _P, _P]),
     "semtsdf_icp_system": (_I, [_P, C.POINTER(IcpIn), _P, _P, _F, _F, C.c_int32, _P, _P]),
     "semtsdf_icp_system_dev": (_I, [_P, C.POINTER(IcpIn), _P, _P, _F, _F, C.c_int32, _P, _P]),
+    "semtsdf_frame_levels": (_I, [_P, _I, C.POINTER(FrameLevel)]),
+    "semtsdf_frame_pyramid": (_I, [_P, _P, _I, _F, _F, _I, C.POINTER(FrameLevel), _P]),
+    "semtsdf_frame_pyramid_dev": (_I, [_P, _P, _I, _F, _F, _I, C.POINTER(FrameLevel), _P]),
+    "semtsdf_icp_system_level": (_I, [_P, C.POINTER(IcpIn), C.c_int32, C.c_int32, _P, _P, _F, _F, C.c_int32, _P, _P]),
+    "semtsdf_icp_system_level_dev": (_I, [_P, C.POINTER(IcpIn), C.c_int32, C.c_int32, _P, _P, _F, _F, C.c_int32, _P,
+                                          _P]),
     "semtsdf_shard_ray_begin": (_I, [_P, _I, _P, _P, _I, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "semtsdf_shard_ray_step": (_I, [_P, _I, _P, _P, _P]),
     "semtsdf_shard_render_finish": (_I, [_P, _P, _P, _P, _P]),

@@ -4,7 +4,9 @@ The device does the per-pixel work (include/semtsdf.h, "camera tracking"): the m
 reference view (semtsdf_render_maps_dev), the frame maps of the depth image
 (semtsdf_frame_maps_dev) and, per iteration, the normal equations as 32 fixed-point int64 words
 (semtsdf_icp_system_dev).  This module is the host side, NumPy float64 like pose.py: it scales the
-words back, solves the 6 x 6 system and moves the pose.
+words back, solves the 6 x 6 system and moves the pose.  track_pyramid runs the same loop coarse to
+fine on the depth pyramid (include/semtsdf.h, "depth pyramid": semtsdf_frame_pyramid_dev,
+semtsdf_icp_system_level_dev) against the one full-resolution render of the model.
 
 Conventions.  E is the integrate's extrinsic: volume frame to camera, so C2W = E^-1 is the camera's
 pose in the volume frame.  A step is a twist xi = (omega, v) of the volume frame:
@@ -168,6 +170,89 @@ def track(vol, depth, E_ref, E0, iters=10, dist_max=0.1, cos_min=0.8, stride=1, 
             b.free()
 
 
+# (level, max iterations, dist_max, cos_min), coarse first: the gates open where the smoothed coarse
+# normals can bear it and close again at full resolution
+PYRAMID_SCHEDULE = ((2, 4, 0.3, 0.6), (1, 5, 0.2, 0.7), (0, 10, 0.1, 0.8))
+
+
+def pyramid_loop(system, dims, E0, schedule=PYRAMID_SCHEDULE, stride=1, min_inliers=None, eps=STEP_EPS):
+    """The coarse-to-fine loop over any source of the words: system(level, E_cur, dist_max,
+    cos_min) -> 32 int64 words, `dims[level]` = (width, height) of that level's frame grid.  Each
+    schedule entry runs track_loop from the previous entry's result, with default_min_inliers of
+    its level's grid unless min_inliers is given.  Returns (E, log); every log entry carries its
+    `level`.  TrackingLost carries the estimate reached and the log of all levels so far."""
+    E = np.asarray(E0, np.float32).reshape(4, 4).copy()
+    log = []
+    for level, iters, dist_max, cos_min in schedule:
+        level = int(level)
+        w, h = dims[level]
+        need = default_min_inliers(w, h, int(stride)) if min_inliers is None else min_inliers
+
+        def tag(entries):
+            return [dict(e, level=level) for e in entries]
+
+        try:
+            E, part = track_loop(lambda Ec: system(level, Ec, dist_max, cos_min), E, iters, need, eps)
+        except TrackingLost as e:
+            raise TrackingLost(f"level {level}: {e}", e.E, log + tag(e.log)) from e
+        log += tag(part)
+    return E, log
+
+
+def track_pyramid(vol, depth, E_ref, E0, schedule=PYRAMID_SCHEDULE, radius=3, sigma_r=0.05, band=None, stride=1,
+                  min_weight=1, min_inliers=None, eps=STEP_EPS):
+    """track() coarse to fine on the depth pyramid (Volume.frame_pyramid_dev: the edge-preserving
+    filter of `radius`, `sigma_r`, halvings within `band`).  The model maps are rendered once at full
+    resolution and the pyramid is built once, as many levels as the schedule's coarsest entry needs;
+    everything stays on the device and each iteration is one launch (icp_system_level_dev) and a
+    256-byte read-back.  Returns (E, log) as pyramid_loop does, and raises TrackingLost like it."""
+    from .maps import pose_camera
+    from .volume import DeviceBuffer
+
+    d = np.ascontiguousarray(depth, dtype=np.uint16)
+    n = vol.W * vol.H
+    if d.size != n:
+        raise ValueError(f"depth must be {vol.H}x{vol.W} u16")
+    schedule = tuple(tuple(s) for s in schedule)
+    if not schedule or min(int(s[0]) for s in schedule) < 0:
+        raise ValueError("schedule: (level, iterations, dist_max, cos_min) entries with level >= 0")
+    nlevels = max(int(s[0]) for s in schedule) + 1
+    geo = vol.frame_levels(nlevels)
+    E_ref = L.f32(E_ref, 16)
+    s2w, c = pose_camera(list(vol.params.Kinv), E_ref)
+    stream = C.c_void_p(vol.stream)
+    sizes = {"depth": 2 * n, "m_point": 12 * n, "m_normal": 12 * n, "m_flags": n, "words": 8 * L.ICP_WORDS}
+    for l, g in enumerate(geo):
+        m = g["width"] * g["height"]
+        sizes.update({f"z{l}": 4 * m, f"vertex{l}": 12 * m, f"normal{l}": 12 * m, f"flags{l}": m})
+    bufs = {}
+    try:
+        for k, size in sizes.items():
+            bufs[k] = DeviceBuffer(size)
+        vol.render_maps_dev(s2w, c, int(min_weight), point=bufs["m_point"].ptr, normal=bufs["m_normal"].ptr,
+                            flags=bufs["m_flags"].ptr)
+        bufs["depth"].upload(d, stream)
+        vol.frame_pyramid_dev(bufs["depth"].ptr, [{k: bufs[f"{k}{l}"].ptr for k in ("z", "vertex", "normal", "flags")}
+                                                  for l in range(nlevels)], radius, sigma_r, band)
+        model = [bufs[k].ptr for k in ("m_point", "m_normal", "m_flags")]
+        words = np.zeros(L.ICP_WORDS, np.int64)
+
+        def system(level, E, dist_max, cos_min):
+            frame = [bufs[f"{k}{level}"].ptr for k in ("vertex", "normal", "flags")]
+            vol.icp_system_level_dev(frame + model, geo[level]["width"], geo[level]["height"], E_ref, E, dist_max,
+                                     cos_min, stride, bufs["words"].ptr)
+            bufs["words"].download(words, stream)
+            vol.sync()
+            return words
+
+        dims = [(g["width"], g["height"]) for g in geo]
+        return pyramid_loop(system, dims, E0, schedule, stride, min_inliers, eps)
+    finally:
+        vol.sync()
+        for b in bufs.values():
+            b.free()
+
+
 def pose_errors(E, E_true):
     """(translation error in metres, rotation angle in radians) between two extrinsics, measured
     on the camera poses C2W = E^-1."""
@@ -179,4 +264,4 @@ def pose_errors(E, E_true):
 
 
 __all__ = ["TrackingLost", "system_from_words", "solve_step", "se3_exp", "se3_apply", "track_loop", "track",
-           "pose_errors", "default_min_inliers", "STEP_EPS"]
+           "pose_errors", "default_min_inliers", "STEP_EPS", "PYRAMID_SCHEDULE", "pyramid_loop", "track_pyramid"]

@@ -319,6 +319,101 @@ class Volume:
                                                 L.ptr(er), L.ptr(ec), float(dist_max), float(cos_min), int(stride),
                                                 C.c_void_p(words_ptr) if words_ptr else None, stream))
 
+    # ---- depth pyramid (semtsdf/track.py's track_pyramid drives these)
+    @staticmethod
+    def _pyramid_band(radius, sigma_r, band, nlevels):
+        if band is None:
+            if int(radius) == 0 and int(nlevels) > 1:
+                raise ValueError("band must be given when radius is 0 (its default is 3 * sigma_r of the filter)")
+            band = 3.0 * float(sigma_r)
+        return float(band)
+
+    def frame_levels(self, nlevels: int = 3) -> list:
+        """Width, height and Kinv (f32 [3, 3]) of the pyramid's levels (semtsdf_frame_levels); no device work."""
+        lv = (L.FrameLevel * L.PYRAMID_MAX_LEVELS)()
+        L.check(L.load().semtsdf_frame_levels(self._h, int(nlevels), lv))
+        return [{"width": int(v.width), "height": int(v.height),
+                 "Kinv": np.array(v.Kinv[:], np.float32).reshape(3, 3)} for v in lv[:int(nlevels)]]
+
+    def frame_pyramid(self, depth, nlevels: int = 3, radius: int = 3, sigma_r: float = 0.05, band=None,
+                      want=("vertex", "normal", "flags")) -> list:
+        """The depth pyramid of a depth image and the frame maps of its levels (semtsdf_frame_pyramid):
+        one dict per level with width, height, Kinv, z (f32 [h, w], metres, 0 = no depth) and the
+        maps named in `want` (vertex, normal f32 [h, w, 3]; flags u8 [h, w]).  Level 0 is the depth
+        through the edge-preserving filter of `radius` and `sigma_r` (radius 0: unfiltered), each
+        further level a halving within `band` metres, by default 3 * sigma_r (to be given when
+        radius is 0)."""
+        d = np.ascontiguousarray(depth, dtype=np.uint16)
+        if d.size != self.W * self.H:
+            raise ValueError(f"depth must be {self.H}x{self.W} u16")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        bad = [w for w in want if w not in ("vertex", "normal", "flags")]
+        if bad:
+            raise ValueError(f"unknown frame map {bad[0]!r} (one of vertex, normal, flags)")
+        band = self._pyramid_band(radius, sigma_r, band, nlevels)
+        out = self.frame_levels(nlevels)  # refuses a bad nlevels before anything is sized by it
+        lv = (L.FrameLevel * L.PYRAMID_MAX_LEVELS)()
+        for o, v in zip(out, lv):
+            h, w = o["height"], o["width"]
+            o["z"] = np.zeros((h, w), np.float32)
+            for name in want:
+                o[name] = np.zeros((h, w) if name == "flags" else (h, w, 3), np.uint8 if name == "flags" else np.float32)
+            v.z = o["z"].ctypes.data
+            for name in want:
+                setattr(v, name, o[name].ctypes.data)
+        L.check(L.load().semtsdf_frame_pyramid(self._h, L.ptr(d), int(radius), float(sigma_r), band, int(nlevels), lv,
+                                               None))
+        return out
+
+    def frame_pyramid_dev(self, depth_ptr: int, levels, radius: int = 3, sigma_r: float = 0.05, band=None,
+                          stream=None) -> list:
+        """frame_pyramid from and into device buffers, asynchronous on `stream`: `levels` holds one
+        dict per level with the raw device pointer "z" and optionally "vertex", "normal", "flags".
+        Returns the levels' width, height and Kinv as frame_levels does."""
+        nlevels = len(levels)
+        band = self._pyramid_band(radius, sigma_r, band, nlevels)
+        lv = (L.FrameLevel * max(nlevels, L.PYRAMID_MAX_LEVELS))()  # the library refuses a bad count
+        for o, v in zip(levels, lv):
+            for name in ("z", "vertex", "normal", "flags"):
+                setattr(v, name, int(o[name]) if o.get(name) else None)
+        L.check(L.load().semtsdf_frame_pyramid_dev(self._h, C.c_void_p(depth_ptr) if depth_ptr else None, int(radius),
+                                                   float(sigma_r), band, nlevels, lv, stream))
+        return [{"width": int(v.width), "height": int(v.height),
+                 "Kinv": np.array(v.Kinv[:], np.float32).reshape(3, 3)} for v in lv[:nlevels]]
+
+    def icp_system_level(self, frame: dict, model: dict, E_ref, E_cur, dist_max: float = 0.1, cos_min: float = 0.8,
+                         stride: int = 1) -> np.ndarray:
+        """icp_system with the frame maps on a grid of their own (semtsdf_icp_system_level): `frame`
+        a level of frame_pyramid ([h, w] taken from its flags), `model` the full-resolution point,
+        normal, flags of render_maps at pose_camera(Kinv, E_ref)."""
+        fl = np.ascontiguousarray(frame["flags"], np.uint8)
+        if fl.ndim != 2:
+            raise ValueError("frame flags must be [h, w]")
+        fh, fw = fl.shape
+        n = self.W * self.H
+        arrs = [np.ascontiguousarray(frame["vertex"], np.float32), np.ascontiguousarray(frame["normal"], np.float32),
+                fl, np.ascontiguousarray(model["point"], np.float32),
+                np.ascontiguousarray(model["normal"], np.float32), np.ascontiguousarray(model["flags"], np.uint8)]
+        for a, size in zip(arrs, (fw * fh * 3, fw * fh * 3, fw * fh, n * 3, n * 3, n)):
+            if a.size != size:
+                raise ValueError(f"frame maps must be {fh}x{fw}, model maps {self.H}x{self.W}")
+        words = np.zeros(L.ICP_WORDS, np.int64)
+        er, ec = L.f32(E_ref, 16), L.f32(E_cur, 16)
+        L.check(L.load().semtsdf_icp_system_level(self._h, C.byref(L.IcpIn(*[a.ctypes.data for a in arrs])), fw, fh,
+                                                  L.ptr(er), L.ptr(ec), float(dist_max), float(cos_min), int(stride),
+                                                  L.ptr(words), None))
+        return words
+
+    def icp_system_level_dev(self, pointers, frame_width: int, frame_height: int, E_ref, E_cur, dist_max, cos_min,
+                             stride, words_ptr: int, stream=None):
+        """icp_system_level on device buffers: `pointers` as icp_system_dev takes them, the frame's
+        three on a frame_width x frame_height grid; asynchronous on `stream`, nothing is read back."""
+        er, ec = L.f32(E_ref, 16), L.f32(E_cur, 16)
+        L.check(L.load().semtsdf_icp_system_level_dev(
+            self._h, C.byref(L.IcpIn(*[int(p) if p else None for p in pointers])), int(frame_width), int(frame_height),
+            L.ptr(er), L.ptr(ec), float(dist_max), float(cos_min), int(stride),
+            C.c_void_p(words_ptr) if words_ptr else None, stream))
+
     # ---- state transfer (reference layouts)
     def download(self, sdf=True, wt=True, color=True, hist=False, cls=False):
         n = self.nvox
