@@ -2131,7 +2131,7 @@ static int color_xfer(semtsdf_vol* v, void* host, bool to_host, hipStream_t s, u
         return to_host ? launch_color_chunk(v->b.color, stage, true, i32, v->color_wide, v->g, v0, nv, s)
                        : launch_color_chunk(stage, v->b.color, false, i32, v->color_wide, v->g, v0, nv, s);
     };
-    return staged_xfer(host, vb, ve, i32 ? 12 : 3, 1ull << 24, to_host, "colour", s, conv);
+    return staged_xfer(host, vb, ve, i32 ? 12 : 3, kColorChunk, to_host, "colour", s, conv);
 }
 
 // the histogram between the device's layout and the reference [N][32] layout, <= 512 MiB staging
@@ -2140,7 +2140,7 @@ static int hist_xfer(semtsdf_vol* v, uint32_t* host, bool to_host, hipStream_t s
         return to_host ? launch_hist_chunk_to_vm(v->b.hist, static_cast<uint32_t*>(stage), v->g, v0, nv, s)
                        : launch_hist_chunk_to_bm(static_cast<uint32_t*>(stage), v->b.hist, v->g, v0, nv, s);
     };
-    return staged_xfer(host, vb, ve, kMaxObjects * 4, 1ull << 22, to_host, "histogram", s, conv);
+    return staged_xfer(host, vb, ve, kMaxObjects * 4, kHistChunk, to_host, "histogram", s, conv);
 }
 
 int semtsdf_download_slab(semtsdf_vol* v, int x0, int x1, float* sdf, int32_t* wt, void* color, uint32_t* hist,

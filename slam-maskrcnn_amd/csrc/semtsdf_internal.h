@@ -384,6 +384,20 @@ struct ShardRayArgs {
     long long* partial;       // [kAssocPartialLen]
 };
 
+// Grid caps of the kernels that walk the stored volume (blocks of 256 threads; a capped grid loops
+// over the rest) and the staging chunks of the uploads and downloads (reference voxels).  Each is a
+// row of DESIGN.md's "Long walks" table, which names the test that takes its second trip;
+// tests/test_long_walks.py compares these values with tests/long_walk_fields.py.
+constexpr unsigned kMinBlocks = 4096;        // launch_min_i64
+constexpr unsigned kHistMaskBlocks = 16384;  // launch_hist_mask
+constexpr unsigned kXferBlocks = 16384;      // launch_hist_chunk_to_vm / _to_bm, launch_vox_chunk, launch_color_chunk
+constexpr unsigned kWidenBlocks = 65536;     // launch_weight_widen, launch_color_widen
+constexpr unsigned kExportBlocks = 65536;    // launch_export_surface
+constexpr unsigned kRemapBlocks = 16384;     // launch_remap_instances
+constexpr unsigned kInstBlocks = 2048;       // launch_instance_stats: 8 blocks of 4 waves on each of 256 CUs
+constexpr uint64_t kHistChunk = 1ull << 22;  // hist_xfer: 512 MiB of staging
+constexpr uint64_t kColorChunk = 1ull << 24;  // color_xfer
+
 // ---- launchers (semtsdf_kernels.hip) ----
 hipError_t launch_shard_ray_step(const ShardRayArgs& a, hipStream_t s);
 hipError_t launch_shard_render_final(const ShardRayArgs& a, hipStream_t s);

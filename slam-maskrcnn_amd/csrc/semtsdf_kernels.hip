@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void k_min_i64(long long* __restrict__ dst, co
 
 hipError_t launch_min_i64(long long* dst, const long long* src, size_t n, hipStream_t s) {
     size_t blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
+    if (blocks > kMinBlocks) blocks = kMinBlocks;
     if (blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(k_min_i64, dim3((unsigned)blocks), dim3(256), 0, s, dst, src, n);
     return hipGetLastError();
@@ -4374,7 +4374,7 @@ __global__ __launch_bounds__(256) void k_hist_mask(VolGeom g, const uint32_t* __
 hipError_t launch_hist_mask(const VolGeom& g, const VolBufs& b, hipStream_t s) {
     if (!b.hist || !b.hmask || g.nvox == 0) return hipSuccess;
     uint64_t blocks = (g.nvox + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
+    if (blocks > kHistMaskBlocks) blocks = kHistMaskBlocks;
     hipLaunchKernelGGL(k_hist_mask, dim3((unsigned)blocks), dim3(256), 0, s, g, b.hist, b.hmask);
     return hipGetLastError();
 }
@@ -4401,7 +4401,7 @@ __global__ __launch_bounds__(256) void k_hist_to_bm(VolGeom g, const uint32_t* _
 hipError_t launch_hist_chunk_to_vm(const uint32_t* bm, uint32_t* vm, const VolGeom& g, uint64_t v0, uint64_t nv,
                                    hipStream_t s) {
     uint64_t blocks = (nv * kMaxObjects + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
+    if (blocks > kXferBlocks) blocks = kXferBlocks;
     hipLaunchKernelGGL(k_hist_to_vm, dim3((unsigned)blocks), dim3(256), 0, s, g, bm, vm, v0, nv);
     return hipGetLastError();
 }
@@ -4409,7 +4409,7 @@ hipError_t launch_hist_chunk_to_vm(const uint32_t* bm, uint32_t* vm, const VolGe
 hipError_t launch_hist_chunk_to_bm(const uint32_t* vm, uint32_t* bm, const VolGeom& g, uint64_t v0, uint64_t nv,
                                    hipStream_t s) {
     uint64_t blocks = (nv * kMaxObjects + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
+    if (blocks > kXferBlocks) blocks = kXferBlocks;
     hipLaunchKernelGGL(k_hist_to_bm, dim3((unsigned)blocks), dim3(256), 0, s, g, vm, bm, v0, nv);
     return hipGetLastError();
 }
@@ -4434,7 +4434,7 @@ __global__ __launch_bounds__(256) void k_vox_from_ref(VolGeom g, const uint32_t*
 hipError_t launch_vox_chunk(const void* src, void* dst, bool to_ref, const VolGeom& g, uint64_t v0, uint64_t nv,
                             hipStream_t s, bool dev_u16) {
     uint64_t blocks = (nv + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
+    if (blocks > kXferBlocks) blocks = kXferBlocks;
     if (blocks == 0) return hipSuccess;
     if (to_ref && dev_u16)
         hipLaunchKernelGGL(k_vox_to_ref<uint16_t>, dim3((unsigned)blocks), dim3(256), 0, s, g, (const uint16_t*)src, (uint32_t*)dst, v0, nv);
@@ -4485,7 +4485,7 @@ __global__ __launch_bounds__(256) void k_weight_widen(const uint16_t* __restrict
 hipError_t launch_weight_widen(const uint16_t* narrow, int32_t* wide, uint64_t nvox, hipStream_t s) {
     if (nvox == 0) return hipSuccess;
     uint64_t blocks = (nvox + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
+    if (blocks > kWidenBlocks) blocks = kWidenBlocks;
     hipLaunchKernelGGL(k_weight_widen, dim3((unsigned)blocks), dim3(256), 0, s, narrow, wide, nvox);
     return hipGetLastError();
 }
@@ -4493,7 +4493,7 @@ hipError_t launch_weight_widen(const uint16_t* narrow, int32_t* wide, uint64_t n
 hipError_t launch_color_widen(const uint8_t* narrow, int32_t* wide, uint64_t nvox, hipStream_t s) {
     if (nvox == 0) return hipSuccess;
     uint64_t blocks = (nvox + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
+    if (blocks > kWidenBlocks) blocks = kWidenBlocks;
     hipLaunchKernelGGL(k_color_widen, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(narrow),
                        reinterpret_cast<int4*>(wide), nvox);
     return hipGetLastError();
@@ -4511,7 +4511,7 @@ static void color_chunk_t(const void* src, void* dst, bool to_ref, const VolGeom
 hipError_t launch_color_chunk(const void* src, void* dst, bool to_ref, bool ref_i32, bool dev_i32, const VolGeom& g,
                               uint64_t v0, uint64_t nv, hipStream_t s) {
     uint64_t blocks = (nv * 3 + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
+    if (blocks > kXferBlocks) blocks = kXferBlocks;
     const dim3 gr((unsigned)blocks);
     if (dev_i32)
         color_chunk_t<int32_t, int32_t>(src, dst, to_ref, g, v0, nv, gr, s);
@@ -4847,8 +4847,8 @@ hipError_t launch_export_surface(const VolGeom& g, const VolBufs& b, float sdf_m
     const uint64_t n = (uint64_t)g.dimx * g.dimy * g.lz;
     if (n == 0) return hipSuccess;
     const uint64_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(k_export_surface, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, g, b, sdf_max,
-                       min_w, color_wide, semantic, out, cap, count);
+    hipLaunchKernelGGL(k_export_surface, dim3((unsigned)(blocks < kExportBlocks ? blocks : kExportBlocks)), dim3(256), 0, s,
+                       g, b, sdf_max, min_w, color_wide, semantic, out, cap, count);
     return hipGetLastError();
 }
 
@@ -5225,7 +5225,6 @@ hipError_t launch_mesh_emit(const VolGeom& g, const VolBufs& b, int min_w, int c
 // ------------------------------------------------------------------------------------
 constexpr int kInstSums = 9;  // the u64 sums leading InstanceRec
 static_assert(offsetof(InstanceRec, min) == kInstSums * 8 && sizeof(InstanceRec) == 96, "InstanceRec layout");
-constexpr unsigned kInstBlocks = 2048;  // persistent grid: 8 blocks of 4 waves on each of 256 CUs
 
 __global__ __launch_bounds__(256) void k_instance_clear(InstanceRec* __restrict__ rec,
                                                         unsigned long long* __restrict__ overlap) {
@@ -5400,8 +5399,8 @@ __global__ __launch_bounds__(256) void k_remap_instances(VolGeom g, uint32_t* hi
 hipError_t launch_remap_instances(const VolGeom& g, const VolBufs& b, RemapLut lut, uint32_t moved, hipStream_t s) {
     if (!b.hist || !b.hmask || g.nvox == 0 || moved == 0u) return hipSuccess;
     const uint64_t blocks = g.nvox >> 8;
-    hipLaunchKernelGGL(k_remap_instances, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, s, g, b.hist,
-                       b.hmask, lut, moved);
+    hipLaunchKernelGGL(k_remap_instances, dim3((unsigned)(blocks < kRemapBlocks ? blocks : kRemapBlocks)), dim3(256), 0, s, g,
+                       b.hist, b.hmask, lut, moved);
     return hipGetLastError();
 }
 
