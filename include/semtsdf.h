@@ -472,6 +472,105 @@ int semtsdf_icp_system_level_dev(semtsdf_vol* v, const semtsdf_icp_in* in_dev, i
                                  int32_t frame_height, const float E_ref[16], const float E_cur[16], float dist_max,
                                  float cos_min, int32_t stride, int64_t* words_dev, void* stream);
 
+/* ---- RGB-D tracking: a photometric term beside point-to-plane ICP (no reference counterpart) --------
+ * Point-to-plane ICP has no constraint along a plane or around its normal.  A dense photometric term
+ * between the frame's colour image and the colour render of the model (semtsdf_raycast,
+ * SEMTSDF_RENDER_COLOR, at semtsdf_pose_camera(Kinv, E_ref): the view of the model maps, same t) adds
+ * one.  Two calls: the intensity pyramid of a colour image, and the system of one iteration with both
+ * terms, 64 words from one launch.  W, H, K are the handle's; no call reads or modifies the volume.
+ *
+ * Intensity pyramid.  Input: a u8 x 3 image [H*W*3], an optional u8 validity image [H*W] (nonzero =
+ * valid, NULL = all valid), nlevels in 1..SEMTSDF_PYRAMID_MAX_LEVELS.  Level l is (W >> l) x (H >> l),
+ * the depth pyramid's sizes.  Everything is an integer until one exact conversion:
+ *   Y = c0 + 2 c1 + c2 of the three channels (symmetric in the outer two: RGB and BGR images agree).
+ *   S_0(x, y) = sum over dy, dx in -1..1 of b(dy) b(dx) Y(clamp(x + dx, 0, W - 1), clamp(y + dy, 0, H - 1))
+ *     with b = (1, 2, 1): at most 16 * 1020 = 16320.  valid_0(x, y) = 1 iff all nine clamped taps are
+ *     valid, else 0.
+ *   S_{l+1}(x, y) = S_l(2x, 2y) + S_l(2x + 1, 2y) + S_l(2x, 2y + 1) + S_l(2x + 1, 2y + 1);  valid_{l+1} = 1
+ *     iff all four are valid.
+ *   The intensity of a pixel of level l is I = (float)S_l * 2^-(14 + 2l), exact and in [0, 1).
+ * semtsdf_intensity_level: width and height are written by the library; S (u32) and valid (u8) are
+ * both required at every level.  One launch builds all levels.
+ * semtsdf_intensity_pyramid_dev: device pointers (rgb_d, valid_d and those in the structs, which stay
+ *   host memory); allocates nothing, one launch on the stream, reads nothing back.
+ * semtsdf_intensity_pyramid: host pointers; synchronises.  Its device scratch (4 B per pixel, 5 B per
+ *   pixel of each of the four levels the image admits, and 10 B per pixel with 512 B for the host
+ *   variant of the system below) is the handle's, counted in device_bytes and kept after the first
+ *   call; failing to get it is SEMTSDF_ERR_OOM and the handle stays usable.
+ * Errors, all decided before any device work: a NULL argument other than valid, a NULL S or valid of
+ * a level, nlevels outside 1..SEMTSDF_PYRAMID_MAX_LEVELS, a coarsest level narrower or lower than 2
+ * pixels: SEMTSDF_ERR_INVALID.  A Z-sharded handle: SEMTSDF_ERR_UNSUPPORTED.
+ *
+ * The RGB-D system of one iteration, on pyramid level l.  Inputs: semtsdf_icp_in with the frame maps
+ * of level l of the depth pyramid ((W >> l) x (H >> l); level 0 may be semtsdf_frame_maps') and the
+ * full-resolution model maps of the reference view, as for semtsdf_icp_system_level; semtsdf_rgbd_in:
+ * S_l and valid_l of the frame's colour image and of the model's colour render, the latter built with
+ * the validity (m_flags & 3) == 3 (SEMTSDF_MAP_NORMAL says that the eight corners of the colour sample
+ * were observed); r_max, the gate on the intensity residual.  On the host, before the launch: Rt, o,
+ * dmax2 as for semtsdf_icp_system; the level camera as semtsdf_frame_levels forms it, in double,
+ * rounded once to f32: fx_l = K[0] / 2^l, fy_l = K[5] / 2^l, cx_l = (K[2] + 0.5) / 2^l - 0.5, cy_l likewise.
+ * w_l = W >> l, h_l = H >> l.
+ * Words 0..31 are semtsdf_icp_system_level's on the same inputs with frame_width = w_l and
+ * frame_height = h_l, by its rule, untouched.
+ * Words 32..63 are the photometric system in the same layout (21 upper-triangle words, 6 of J^T r, the
+ * sum of r^2, then the counts of inliers, far, outlier, none).  Every frame pixel (x, y) on the stride
+ * with frame flags bit 0 set and the frame's valid_l set is visited and falls into exactly one class,
+ * by these steps in order.  All arithmetic is f32, every operation rounded on its own unless written
+ * fmaf; dot3 and cross are those of the camera tracking section.
+ *  1. Pw as step 1 of semtsdf_icp_system.
+ *  2. q, s, u, v as its step 2 (the full-resolution projection).  Class none if q[2] <= 0, if (u, v) is
+ *     off the image (not 0 <= u < W and 0 <= v < H, compared as floats) or if the model flags at (u, v)
+ *     lack SEMTSDF_MAP_HIT.  Pm: the model point there.
+ *  3. d[a] = Pm[a] - Pw[a].  Class far if dot3(d, d) > dmax2: the occlusion gate.
+ *  4. iz = 1.0f / q[2];  ul = fmaf(fx_l, q[0] * iz, cx_l), vl = fmaf(fy_l, q[1] * iz, cy_l);  x0 =
+ *     floorf(ul), y0 = floorf(vl).  Class none unless 0 <= x0, x0 + 1 < w_l, 0 <= y0, y0 + 1 < h_l
+ *     (compared as floats) and the model's valid_l is set at (x0, y0), (x0 + 1, y0), (x0, y0 + 1),
+ *     (x0 + 1, y0 + 1).  ax = ul - x0, ay = vl - y0.
+ *  5. With m00, m10, m01, m11 the model's intensities at those four taps: dx0 = m10 - m00,
+ *     dx1 = m11 - m01, top = fmaf(ax, dx0, m00), bot = fmaf(ax, dx1, m01), Im = fmaf(ay, bot - top, top);
+ *     the exact gradient of that bilinear patch: gx = fmaf(ay, dx1 - dx0, dx0),
+ *     gy = fmaf(ax, (m11 - m10) - (m01 - m00), m01 - m00).
+ *  6. r = If - Im with If the frame's intensity at (x, y).  Class outlier if fabsf(r) > r_max.
+ *  7. a0 = (gx * fx_l) * iz, a1 = (gy * fy_l) * iz, a2 = -((a0 * q[0] + a1 * q[1]) * iz): the gradient of
+ *     Im by q.  aw[k] = dot3((E_ref[0][k], E_ref[1][k], E_ref[2][k]), (a0, a1, a2)): by Pw.
+ *     J = (cross(Pw, aw), aw).  Class none unless every |J[i]| < 2048 (a NaN is out of range).
+ *  8. Inlier.  Each product J[i] * J[j] (i <= j), J[i] * r and r * r is formed in double, multiplied by
+ *     2^20, rounded to nearest-even to int64 and added to its word.
+ * C2W <- exp(xi) C2W moves Pw by omega x Pw + v, so Im changes by J . xi to first order and r - J xi is
+ * the residual after the step: the normal equations and the sign are the point-to-plane system's, and
+ * the two add as (A_g + w^2 A_p) xi = b_g + w^2 b_p for a weight w in metres per unit of intensity.
+ * Each term is below 2^22 * 2^20 = 2^42 and at most 2^19 pixels are visited, so no sum reaches 2^61.
+ * Errors, all decided before any device work: those of semtsdf_icp_system_level; a NULL rgbd_in or
+ * intensity pointer; level outside 0..SEMTSDF_PYRAMID_MAX_LEVELS - 1, or with W >> level or H >> level
+ * below 2; K[1] or K[4] nonzero (the level camera has no skew); r_max outside (0, 1] (a NaN is
+ * outside): SEMTSDF_ERR_INVALID.  A Z-sharded handle: SEMTSDF_ERR_UNSUPPORTED.
+ * semtsdf_rgbd_system_level_dev: device pointers; zeroes the 64 words on the stream, then one launch;
+ *   asynchronous, nothing is read back.
+ * semtsdf_rgbd_system_level: host pointers; uploads the maps and the four intensity arrays, runs the
+ *   same launch and synchronises.  It shares semtsdf_icp_system's scratch and the intensity pyramid's. */
+typedef struct semtsdf_intensity_level {
+    int32_t width, height; /* written by the library */
+    uint32_t* S;           /* [h*w] required */
+    uint8_t* valid;        /* [h*w] required */
+} semtsdf_intensity_level;
+typedef struct semtsdf_rgbd_in { /* level l: [(H >> l) * (W >> l)] */
+    const uint32_t* f_S;     /* the frame's colour image */
+    const uint8_t* f_valid;
+    const uint32_t* m_S;     /* the model's colour render at the reference view */
+    const uint8_t* m_valid;
+} semtsdf_rgbd_in;
+#define SEMTSDF_RGBD_WORDS 64
+int semtsdf_intensity_pyramid(semtsdf_vol* v, const uint8_t* rgb, const uint8_t* valid, int nlevels,
+                              semtsdf_intensity_level* levels_host, void* stream);
+int semtsdf_intensity_pyramid_dev(semtsdf_vol* v, const uint8_t* rgb_d, const uint8_t* valid_d, int nlevels,
+                                  semtsdf_intensity_level* levels_dev, void* stream);
+int semtsdf_rgbd_system_level(semtsdf_vol* v, const semtsdf_icp_in* in_host, const semtsdf_rgbd_in* photo_host,
+                              int32_t level, const float E_ref[16], const float E_cur[16], float dist_max,
+                              float cos_min, float r_max, int32_t stride, int64_t* words_host, void* stream);
+int semtsdf_rgbd_system_level_dev(semtsdf_vol* v, const semtsdf_icp_in* in_dev, const semtsdf_rgbd_in* photo_dev,
+                                  int32_t level, const float E_ref[16], const float E_cur[16], float dist_max,
+                                  float cos_min, float r_max, int32_t stride, int64_t* words_dev, void* stream);
+
 /* ---- Z-sharded raycast (replaces the single-GPU back_proj_kernel
  * tsdf.cu:72-135 and show_tsdf_kernel viewer.cu:17-86 when the volume is split across GPUs)
  * Every shard of a group runs the same call sequence.  Between calls the host exchanges

@@ -144,6 +144,7 @@ struct semtsdf_vol {
     uint8_t* maps_d = nullptr;     // semtsdf_render_maps: the six maps back to back (34 B per pixel)
     uint8_t* track_d = nullptr;    // semtsdf_frame_maps / semtsdf_icp_system: host-variant scratch (52 B per pixel)
     uint8_t* pyramid_d = nullptr;  // semtsdf_frame_pyramid: host-variant scratch (PyramidScratch)
+    uint8_t* intensity_d = nullptr;  // semtsdf_intensity_pyramid / semtsdf_rgbd_system_level: host-variant scratch
     unsigned long long* counters_d = nullptr;
     IntegrateRare* rare_d = nullptr;  // the integrate's rare-path fields (IntegrateArgs::rare)
     float* rcp_table_d = nullptr;    // RN(1/n), n = 1..kRcpTable
@@ -1924,9 +1925,9 @@ static int icp_check(semtsdf_vol* v, const semtsdf_icp_in* in, int32_t fw, int32
     return SEMTSDF_OK;
 }
 
-static int icp_impl(semtsdf_vol* v, const semtsdf_icp_in& in_d, int32_t fw, int32_t fh, const float E_ref[16],
-                    const float E_cur[16], float dist_max, float cos_min, int32_t stride, int64_t* words_d,
-                    hipStream_t s) {
+// The point-to-plane system's kernel arguments (semtsdf_icp_system_level and the RGB-D system share them).
+static IcpArgs icp_args(const semtsdf_vol* v, const semtsdf_icp_in& in_d, int32_t fw, int32_t fh, const float E_ref[16],
+                        const float E_cur[16], float dist_max, float cos_min, int32_t stride, int64_t* words_d) {
     IcpArgs a{};
     a.vertex = in_d.vertex; a.normal = in_d.normal; a.flags = in_d.flags;
     a.m_point = in_d.m_point; a.m_normal = in_d.m_normal; a.m_flags = in_d.m_flags;
@@ -1938,6 +1939,13 @@ static int icp_impl(semtsdf_vol* v, const semtsdf_icp_in& in_d, int32_t fw, int3
     a.width = v->p.width; a.height = v->p.height;
     a.fwidth = fw; a.fheight = fh;
     a.words = reinterpret_cast<long long*>(words_d);
+    return a;
+}
+
+static int icp_impl(semtsdf_vol* v, const semtsdf_icp_in& in_d, int32_t fw, int32_t fh, const float E_ref[16],
+                    const float E_cur[16], float dist_max, float cos_min, int32_t stride, int64_t* words_d,
+                    hipStream_t s) {
+    const IcpArgs a = icp_args(v, in_d, fw, fh, E_ref, E_cur, dist_max, cos_min, stride, words_d);
     HIPC(hipMemsetAsync(words_d, 0, kIcpWords * 8, s));
     HIPC(launch_icp_system(a, s));
     return SEMTSDF_OK;
@@ -2109,6 +2117,146 @@ int semtsdf_frame_pyramid(semtsdf_vol* v, const uint16_t* depth, int radius, flo
             return rc;
     }
     return copies_out(s, {});
+}
+
+// ---- RGB-D tracking: the intensity pyramid and the system with a photometric term ----------------
+// Device scratch of the host-pointer variants (IntensityScratch), allocated on the first use.
+static int intensity_scratch(semtsdf_vol* v) {
+    return v->intensity_d ? 0
+                          : v->pool.alloc((void**)&v->intensity_d,
+                                          IntensityScratch(nullptr, v->p.width, v->p.height, kRgbdWords).bytes);
+}
+
+static int intensity_check(const semtsdf_vol* v, const uint8_t* rgb, int nlevels, const semtsdf_intensity_level* levels) {
+    if (!v || !rgb || !levels) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
+    if (nlevels < 1 || nlevels > kPyramidMaxLevels)
+        return fail(SEMTSDF_ERR_INVALID, "nlevels=%d outside 1..%d", nlevels, kPyramidMaxLevels);
+    if ((v->p.width >> (nlevels - 1)) < 2 || (v->p.height >> (nlevels - 1)) < 2)
+        return fail(SEMTSDF_ERR_INVALID, "level %d of a %d x %d image is narrower or lower than 2 pixels", nlevels - 1,
+                    v->p.width, v->p.height);
+    for (int l = 0; l < nlevels; ++l)
+        if (!levels[l].S || !levels[l].valid) return fail(SEMTSDF_ERR_INVALID, "NULL S or valid of level %d", l);
+    if (v->p.z_nshards != 1)
+        return fail(SEMTSDF_ERR_UNSUPPORTED, "the intensity pyramid on a Z-sharded handle is not supported");
+    return SEMTSDF_OK;
+}
+
+static int intensity_impl(semtsdf_vol* v, const uint8_t* rgb_d, const uint8_t* valid_d, int nlevels,
+                          semtsdf_intensity_level* lv, hipStream_t s) {
+    IntensityArgs a{};
+    a.rgb = rgb_d; a.valid = valid_d;
+    a.width = v->p.width; a.height = v->p.height;
+    a.nlevels = nlevels;
+    for (int l = 0; l < nlevels; ++l) {
+        lv[l].width = v->p.width >> l;
+        lv[l].height = v->p.height >> l;
+        a.S[l] = lv[l].S;
+        a.ok[l] = lv[l].valid;
+    }
+    HIPC(launch_intensity_pyramid(a, s));
+    return SEMTSDF_OK;
+}
+
+int semtsdf_intensity_pyramid_dev(semtsdf_vol* v, const uint8_t* rgb_d, const uint8_t* valid_d, int nlevels,
+                                  semtsdf_intensity_level* levels_dev, void* stream) {
+    if (int rc = intensity_check(v, rgb_d, nlevels, levels_dev)) return rc;
+    HIPC(hipSetDevice(v->device));
+    return intensity_impl(v, rgb_d, valid_d, nlevels, levels_dev, pick(v, stream));
+}
+
+int semtsdf_intensity_pyramid(semtsdf_vol* v, const uint8_t* rgb, const uint8_t* valid, int nlevels,
+                              semtsdf_intensity_level* levels_host, void* stream) {
+    if (int rc = intensity_check(v, rgb, nlevels, levels_host)) return rc;
+    HIPC(hipSetDevice(v->device));
+    hipStream_t s = pick(v, stream);
+    if (int rc = intensity_scratch(v)) return rc;
+    const IntensityScratch t(v->intensity_d, v->p.width, v->p.height, kRgbdWords);
+    semtsdf_intensity_level d[kPyramidMaxLevels];
+    for (int l = 0; l < nlevels; ++l) {
+        d[l].S = t.S[l];
+        d[l].valid = t.ok[l];
+    }
+    const size_t n = npx(v);
+    if (int rc = queue_copies(s, hipMemcpyHostToDevice, {{t.rgb, rgb, n * 3}, {t.valid, valid, n}})) return rc;
+    if (int rc = intensity_impl(v, t.rgb, valid ? t.valid : nullptr, nlevels, d, s)) return rc;
+    for (int l = 0; l < nlevels; ++l) {
+        semtsdf_intensity_level& h = levels_host[l];
+        h.width = d[l].width;
+        h.height = d[l].height;
+        const size_t m = (size_t)h.width * (size_t)h.height;
+        if (int rc = queue_copies(s, hipMemcpyDeviceToHost, {{h.S, d[l].S, m * 4}, {h.valid, d[l].valid, m}})) return rc;
+    }
+    return copies_out(s, {});
+}
+
+// Argument checks of the RGB-D system beyond icp_check's, all before any device work.
+static int rgbd_check(semtsdf_vol* v, const semtsdf_icp_in* in, const semtsdf_rgbd_in* photo, int32_t level,
+                      const float* E_ref, const float* E_cur, float dist_max, float cos_min, float r_max, int32_t stride,
+                      const int64_t* words) {
+    if (!v || !photo) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
+    if (level < 0 || level >= kPyramidMaxLevels || (v->p.width >> level) < 2 || (v->p.height >> level) < 2)
+        return fail(SEMTSDF_ERR_INVALID, "level=%d outside the levels of a %d x %d image", (int)level, v->p.width,
+                    v->p.height);
+    if (int rc = icp_check(v, in, v->p.width >> level, v->p.height >> level, E_ref, E_cur, dist_max, cos_min, stride, words))
+        return rc;
+    if (!photo->f_S || !photo->f_valid || !photo->m_S || !photo->m_valid)
+        return fail(SEMTSDF_ERR_INVALID, "NULL intensity input");
+    if (v->p.K[1] != 0.0f || v->p.K[4] != 0.0f)
+        return fail(SEMTSDF_ERR_INVALID, "the photometric term needs K[1] = K[4] = 0 (no skew)");
+    if (!(r_max > 0.0f && r_max <= 1.0f)) return fail(SEMTSDF_ERR_INVALID, "r_max=%g outside (0, 1]", (double)r_max);
+    return SEMTSDF_OK;
+}
+
+static int rgbd_impl(semtsdf_vol* v, const semtsdf_icp_in& in_d, const semtsdf_rgbd_in& ph_d, int32_t level,
+                     const float E_ref[16], const float E_cur[16], float dist_max, float cos_min, float r_max,
+                     int32_t stride, int64_t* words_d, hipStream_t s) {
+    RgbdArgs g{};
+    g.icp = icp_args(v, in_d, v->p.width >> level, v->p.height >> level, E_ref, E_cur, dist_max, cos_min, stride, words_d);
+    g.f_S = ph_d.f_S; g.f_ok = ph_d.f_valid; g.m_S = ph_d.m_S; g.m_ok = ph_d.m_valid;
+    float cam[4];
+    cam_level(cam, v->p.K, level);
+    g.fxl = cam[0]; g.fyl = cam[1]; g.cxl = cam[2]; g.cyl = cam[3];
+    g.iscale = std::ldexp(1.0f, -(14 + 2 * level));
+    g.r_max = r_max;
+    HIPC(hipMemsetAsync(words_d, 0, kRgbdWords * 8, s));
+    HIPC(launch_rgbd_system(g, s));
+    return SEMTSDF_OK;
+}
+
+int semtsdf_rgbd_system_level_dev(semtsdf_vol* v, const semtsdf_icp_in* in_dev, const semtsdf_rgbd_in* photo_dev,
+                                  int32_t level, const float E_ref[16], const float E_cur[16], float dist_max,
+                                  float cos_min, float r_max, int32_t stride, int64_t* words_dev, void* stream) {
+    if (int rc = rgbd_check(v, in_dev, photo_dev, level, E_ref, E_cur, dist_max, cos_min, r_max, stride, words_dev))
+        return rc;
+    HIPC(hipSetDevice(v->device));
+    return rgbd_impl(v, *in_dev, *photo_dev, level, E_ref, E_cur, dist_max, cos_min, r_max, stride, words_dev,
+                     pick(v, stream));
+}
+
+int semtsdf_rgbd_system_level(semtsdf_vol* v, const semtsdf_icp_in* in_host, const semtsdf_rgbd_in* photo_host,
+                              int32_t level, const float E_ref[16], const float E_cur[16], float dist_max,
+                              float cos_min, float r_max, int32_t stride, int64_t* words_host, void* stream) {
+    if (int rc = rgbd_check(v, in_host, photo_host, level, E_ref, E_cur, dist_max, cos_min, r_max, stride, words_host))
+        return rc;
+    HIPC(hipSetDevice(v->device));
+    hipStream_t s = pick(v, stream);
+    if (int rc = track_scratch(v)) return rc;
+    if (int rc = intensity_scratch(v)) return rc;
+    const size_t n = npx(v), nf = (size_t)(v->p.width >> level) * (size_t)(v->p.height >> level);
+    const TrackScratch t{{v->track_d, n}, kIcpWords};
+    const IntensityScratch p(v->intensity_d, v->p.width, v->p.height, kRgbdWords);
+    const semtsdf_icp_in& h = *in_host;
+    const semtsdf_rgbd_in& ph = *photo_host;
+    if (int rc = queue_copies(s, hipMemcpyHostToDevice, {{t.vertex, h.vertex, nf * 12}, {t.normal, h.normal, nf * 12},
+                                                         {t.m_point, h.m_point, n * 12}, {t.m_normal, h.m_normal, n * 12},
+                                                         {t.flags, h.flags, nf}, {t.m_flags, h.m_flags, n},
+                                                         {p.f_S, ph.f_S, nf * 4}, {p.m_S, ph.m_S, nf * 4},
+                                                         {p.f_ok, ph.f_valid, nf}, {p.m_ok, ph.m_valid, nf}}))
+        return rc;
+    const semtsdf_icp_in d{t.vertex, t.normal, t.flags, t.m_point, t.m_normal, t.m_flags};
+    const semtsdf_rgbd_in pd{p.f_S, p.f_ok, p.m_S, p.m_ok};
+    if (int rc = rgbd_impl(v, d, pd, level, E_ref, E_cur, dist_max, cos_min, r_max, stride, p.words, s)) return rc;
+    return copies_out(s, {{words_host, p.words, kRgbdWords * 8}});
 }
 
 // Voxels of the reference layout (rows of lz planes) held by the handle.

@@ -110,6 +110,41 @@ struct PyramidScratch {
     }
 };
 
+// The camera of pyramid level l >= 0 (fx, fy, cx, cy) by cam_level_kinv's rule, each rounded once.
+inline void cam_level(float out[4], const float K[16], int level) {
+    const double s = (double)(1 << level);
+    out[0] = (float)((double)K[0] / s);
+    out[1] = (float)((double)K[5] / s);
+    out[2] = (float)(((double)K[2] + 0.5) / s - 0.5);
+    out[3] = (float)(((double)K[6] + 0.5) / s - 0.5);
+}
+
+// semtsdf_intensity_pyramid and semtsdf_rgbd_system_level: the colour image and its validity (4 B per
+// pixel), S and valid of every level the image admits (5 B per pixel of a level), and the system's
+// four intensity arrays of one level (10 B per pixel) with its words.
+struct IntensityScratch {
+    static constexpr int kLevels = 4;  // SEMTSDF_PYRAMID_MAX_LEVELS
+    Carver c;
+    int64_t* words;
+    uint32_t *S[kLevels], *f_S, *m_S;
+    uint8_t *ok[kLevels], *f_ok, *m_ok, *rgb, *valid;
+    size_t bytes;
+    IntensityScratch(void* base, int width, int height, size_t nwords) : c(base, 0) {
+        size_t n[kLevels];
+        for (int l = 0; l < kLevels; ++l) n[l] = (size_t)(width >> l) * (size_t)(height >> l);
+        words = c.take<int64_t>(0, nwords);
+        for (int l = 0; l < kLevels; ++l) S[l] = c.take<uint32_t>(0, n[l]);
+        f_S = c.take<uint32_t>(0, n[0]);
+        m_S = c.take<uint32_t>(0, n[0]);
+        for (int l = 0; l < kLevels; ++l) ok[l] = c.take<uint8_t>(0, n[l]);
+        f_ok = c.take<uint8_t>(0, n[0]);
+        m_ok = c.take<uint8_t>(0, n[0]);
+        rgb = c.take<uint8_t>(0, 3 * n[0]);
+        valid = c.take<uint8_t>(0, n[0]);
+        bytes = c.bytes;
+    }
+};
+
 // The sharded ray protocol's per-pixel march state (ShardRayState), 24 B per pixel.
 struct RayScratch {
     Carver c;

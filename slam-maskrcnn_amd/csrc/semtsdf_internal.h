@@ -352,6 +352,31 @@ struct DepthHalveArgs {
     float* dst;             // [h >> 1][w >> 1]
 };
 
+// The intensity pyramid of a u8 x 3 image (k_intensity_pyramid): every level from one launch.
+struct IntensityArgs {
+    const uint8_t* rgb;     // [npx][3]
+    const uint8_t* valid;   // [npx], nonzero = valid; null = all valid
+    int width, height;      // level 0
+    int nlevels;            // 1..kPyramidMaxLevels
+    unsigned* S[kPyramidMaxLevels];     // [(h >> l) * (w >> l)] integer intensity sums
+    uint8_t* ok[kPyramidMaxLevels];     // [(h >> l) * (w >> l)] 1 = valid
+};
+
+constexpr int kRgbdWords = 64;  // SEMTSDF_RGBD_WORDS: the geometric system's 32 words, then the photometric 32
+
+// The RGB-D system of one iteration (k_rgbd_system): IcpArgs' inputs on the grid of pyramid level l
+// (fwidth x fheight = (W >> l) x (H >> l)) and both intensity pyramids' level l on that grid.
+struct RgbdArgs {
+    IcpArgs icp;            // words: [kRgbdWords], zeroed before the launch
+    const unsigned* f_S;    // the frame's level l
+    const uint8_t* f_ok;
+    const unsigned* m_S;    // the model's level l
+    const uint8_t* m_ok;
+    float fxl, fyl, cxl, cyl;  // the level camera (double, rounded once)
+    float iscale;           // 2^-(14 + 2 l): intensity of a sum
+    float r_max;
+};
+
 // Z-sharded raycast protocol (k_shard_* in semtsdf_kernels.hip): per-pixel march state.
 struct ShardRayState {
     int* k;      // global coarse event index, -1 = miss
@@ -452,6 +477,8 @@ hipError_t launch_render(const RenderArgs& a, hipStream_t s);
 hipError_t launch_model_maps(const MapsArgs& a, hipStream_t s);
 hipError_t launch_frame_maps(const FrameMapsArgs& a, hipStream_t s);
 hipError_t launch_icp_system(const IcpArgs& a, hipStream_t s);
+hipError_t launch_intensity_pyramid(const IntensityArgs& a, hipStream_t s);
+hipError_t launch_rgbd_system(const RgbdArgs& a, hipStream_t s);
 hipError_t launch_depth_filter(const DepthFilterArgs& a, hipStream_t s);
 hipError_t launch_depth_halve(const DepthHalveArgs& a, hipStream_t s);
 hipError_t launch_march_fused(const AssocArgs& aa, const RenderArgs& ra, hipStream_t s);

@@ -3943,6 +3943,270 @@ hipError_t launch_icp_system(const IcpArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------
+// RGB-D tracking (include/semtsdf.h, "RGB-D tracking"): the intensity pyramid of a colour image and
+// the system of one iteration with a photometric term beside the point-to-plane one.
+// ------------------------------------------------------------------------------------
+constexpr unsigned kIntensityOk = 0x80000000u;  // bit 31 of a staged sum: valid (S_3 <= 16320 * 64 < 2^20)
+
+// One workgroup per 16 x 16 tile of level 0, every level from one launch.  Y = c0 + 2 c1 + c2 of the
+// tile and its one-pixel halo (coordinates clamped to the image) is staged in LDS with the validity in
+// bit 31; S_0 is the 3 x 3 binomial sum, valid iff all nine taps are; each further level is the sum of
+// the 2 x 2 block below it, taken from LDS: the tile origin is a multiple of 16 and (x + 1) 2^l <= W
+// for every pixel of level l (the floors), so the 8 x 8, 4 x 4 and 2 x 2 blocks of a tile are whole.
+__global__ __launch_bounds__(256) void k_intensity_pyramid(IntensityArgs a) {
+    __shared__ unsigned tile[18 * 18];
+    __shared__ unsigned lv[256 + 64 + 16];
+    const int tid = (int)threadIdx.x;
+    const int x0 = (int)blockIdx.x * 16, y0 = (int)blockIdx.y * 16;
+    for (int i = tid; i < 18 * 18; i += 256) {
+        const int ty = i / 18, tx = i - ty * 18;
+        const int gx = min(max(x0 + tx - 1, 0), a.width - 1), gy = min(max(y0 + ty - 1, 0), a.height - 1);
+        const size_t px = (size_t)gy * a.width + gx;
+        const unsigned y = (unsigned)a.rgb[px * 3] + 2u * (unsigned)a.rgb[px * 3 + 1] + (unsigned)a.rgb[px * 3 + 2];
+        tile[i] = y | ((!a.valid || a.valid[px]) ? kIntensityOk : 0u);
+    }
+    __syncthreads();
+    {
+        const int lx = tid & 15, ly = tid >> 4;
+        const unsigned* t = tile + ly * 18 + lx;
+        unsigned sum = 0, ok = kIntensityOk;
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy) {
+            const unsigned p = t[dy * 18], q = t[dy * 18 + 1], r = t[dy * 18 + 2];
+            ok &= p & q & r;
+            const unsigned row = (p & 0xffffu) + 2u * (q & 0xffffu) + (r & 0xffffu);
+            sum += dy == 1 ? 2u * row : row;
+        }
+        lv[tid] = sum | ok;
+        const int x = x0 + lx, y = y0 + ly;
+        if (x < a.width && y < a.height) {
+            const size_t px = (size_t)y * a.width + x;
+            a.S[0][px] = sum;
+            a.ok[0][px] = (uint8_t)(ok >> 31);
+        }
+    }
+    const unsigned* src = lv;
+    unsigned* dst = lv + 256;
+#pragma unroll
+    for (int l = 1; l < kPyramidMaxLevels; ++l) {
+        if (l >= a.nlevels) break;  // uniform: the barrier below is reached by all or none
+        __syncthreads();
+        const int n = 16 >> l;  // the tile's side at level l; the level below is 2 n wide in LDS
+        if (tid < n * n) {
+            const int lx = tid & (n - 1), ly = tid / n;
+            const unsigned* p = src + (2 * ly) * (2 * n) + 2 * lx;
+            const unsigned p0 = p[0], p1 = p[1], p2 = p[2 * n], p3 = p[2 * n + 1];
+            const unsigned ok = p0 & p1 & p2 & p3 & kIntensityOk;
+            const unsigned sum = (p0 & ~kIntensityOk) + (p1 & ~kIntensityOk) + (p2 & ~kIntensityOk) + (p3 & ~kIntensityOk);
+            if (l + 1 < kPyramidMaxLevels) dst[tid] = sum | ok;
+            const int w = a.width >> l, h = a.height >> l;
+            const int x = (x0 >> l) + lx, y = (y0 >> l) + ly;
+            if (x < w && y < h) {
+                const size_t px = (size_t)y * w + x;
+                a.S[l][px] = sum;
+                a.ok[l][px] = (uint8_t)(ok >> 31);
+            }
+        }
+        src = dst;
+        dst += n * n;
+    }
+}
+
+hipError_t launch_intensity_pyramid(const IntensityArgs& a, hipStream_t s) {
+    const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
+    hipLaunchKernelGGL(k_intensity_pyramid, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// RN(a * b * 2^20): the photometric words' scale; |a b| < 2^22 by their range gate.
+__device__ __forceinline__ long long rgbd_fix(float a, float b) {
+    return __double2ll_rn((double)a * (double)b * 1048576.0);
+}
+
+constexpr int kRgbdGrid = 256;  // persistent workgroups at most: one per CU
+
+// At most kRgbdGrid persistent workgroups walk the 16 x 16 tiles of the strided pixel grid with a grid
+// stride, one thread per visited pixel of a tile.  Every lane keeps its 2 x 28 sums in int64 registers
+// across all its tiles and the eight class counts come from ballots; at the end one butterfly per wave,
+// one meeting in LDS and one 64-bit integer atomic per nonzero word per workgroup.  The geometric half
+// is k_icp_system's rule step by step, so words 0..31 are that kernel's.
+__global__ __launch_bounds__(256) void k_rgbd_system(RgbdArgs g, int tiles_x, int ntiles) {
+    __shared__ long long red[4][kRgbdWords];
+    const IcpArgs& a = g.icp;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    long long acc[2 * kIcpSums];
+#pragma unroll
+    for (int k = 0; k < 2 * kIcpSums; ++k) acc[k] = 0;
+    unsigned cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // wave-uniform; at most 2^19 pixels are visited
+    for (int tile = (int)blockIdx.x; tile < ntiles; tile += (int)gridDim.x) {
+        const int by = tile / tiles_x, bx = tile - by * tiles_x;
+        const long long xl = ((long long)bx * 16 + (tid & 15)) * a.stride;
+        const long long yl = ((long long)by * 16 + (tid >> 4)) * a.stride;
+        int cls = -1, pcls = -1;  // 0 inlier, 1 far, 2 angle / outlier, 3 none; -1: not visited
+        float J[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, r = 0.0f;
+        float Jp[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, rp = 0.0f;
+        if (xl < a.fwidth && yl < a.fheight) {
+            const size_t px = (size_t)yl * a.fwidth + (size_t)xl;
+            const unsigned fl = a.flags[px];
+            if ((fl & 3u) == 3u) cls = 3;
+            if ((fl & 1u) && g.f_ok[px]) pcls = 3;
+            if (cls == 3 || pcls == 3) {
+                const float V0 = a.vertex[px * 3 + 0], V1 = a.vertex[px * 3 + 1], V2 = a.vertex[px * 3 + 2];
+                float Pw[3];
+                Pw[0] = dot3(a.Rt[0], a.Rt[1], a.Rt[2], V0, V1, V2) + a.o[0];
+                Pw[1] = dot3(a.Rt[3], a.Rt[4], a.Rt[5], V0, V1, V2) + a.o[1];
+                Pw[2] = dot3(a.Rt[6], a.Rt[7], a.Rt[8], V0, V1, V2) + a.o[2];
+                const float qx = dot3(a.Eref[0], a.Eref[1], a.Eref[2], Pw[0], Pw[1], Pw[2]) + a.Eref[3];
+                const float qy = dot3(a.Eref[4], a.Eref[5], a.Eref[6], Pw[0], Pw[1], Pw[2]) + a.Eref[7];
+                const float qz = dot3(a.Eref[8], a.Eref[9], a.Eref[10], Pw[0], Pw[1], Pw[2]) + a.Eref[11];
+                const float sx = dot3(a.K[0], a.K[1], a.K[2], qx, qy, qz);
+                const float sy = dot3(a.K[3], a.K[4], a.K[5], qx, qy, qz);
+                const float sz = dot3(a.K[6], a.K[7], a.K[8], qx, qy, qz);
+                const float u = floorf(sx / sz + 0.5f), v = floorf(sy / sz + 0.5f);
+                if (!(qz <= 0.0f) && u >= 0.0f && u < (float)a.width && v >= 0.0f && v < (float)a.height) {
+                    const size_t mp = (size_t)(int)v * a.width + (size_t)(int)u;
+                    const unsigned mf = a.m_flags[mp];
+                    if (mf & 1u) {
+                        float d[3];
+                        for (int k = 0; k < 3; ++k) d[k] = a.m_point[mp * 3 + k] - Pw[k];
+                        const bool far = dot3(d[0], d[1], d[2], d[0], d[1], d[2]) > a.dmax2;
+                        if (cls == 3 && (mf & 3u) == 3u) {  // the point-to-plane row: k_icp_system's steps 3..5
+                            if (far) {
+                                cls = 1;
+                            } else {
+                                float Nm[3];
+                                for (int k = 0; k < 3; ++k) Nm[k] = a.m_normal[mp * 3 + k];
+                                const float n0 = a.normal[px * 3 + 0], n1 = a.normal[px * 3 + 1], n2 = a.normal[px * 3 + 2];
+                                const float w0 = dot3(a.Rt[0], a.Rt[1], a.Rt[2], n0, n1, n2);
+                                const float w1 = dot3(a.Rt[3], a.Rt[4], a.Rt[5], n0, n1, n2);
+                                const float w2 = dot3(a.Rt[6], a.Rt[7], a.Rt[8], n0, n1, n2);
+                                if (dot3(Nm[0], Nm[1], Nm[2], w0, w1, w2) < a.cos_min) {
+                                    cls = 2;
+                                } else {
+                                    r = dot3(Nm[0], Nm[1], Nm[2], d[0], d[1], d[2]);
+                                    cross3(Pw, Nm, J);
+                                    J[3] = Nm[0];
+                                    J[4] = Nm[1];
+                                    J[5] = Nm[2];
+                                    bool in = true;
+                                    for (int k = 0; k < 6; ++k) in = in && fabsf(J[k]) < 32.0f;
+                                    if (in) cls = 0;
+                                }
+                            }
+                        }
+                        if (pcls == 3) {  // the photometric row: steps 3..7
+                            if (far) {
+                                pcls = 1;
+                            } else {
+                                const float iz = 1.0f / qz;
+                                const float ul = fmaf(g.fxl, qx * iz, g.cxl), vl = fmaf(g.fyl, qy * iz, g.cyl);
+                                const float fx0 = floorf(ul), fy0 = floorf(vl);
+                                if (fx0 >= 0.0f && fx0 + 1.0f < (float)a.fwidth && fy0 >= 0.0f &&
+                                    fy0 + 1.0f < (float)a.fheight) {
+                                    const size_t lp = (size_t)(int)fy0 * a.fwidth + (size_t)(int)fx0;
+                                    if (g.m_ok[lp] && g.m_ok[lp + 1] && g.m_ok[lp + a.fwidth] && g.m_ok[lp + a.fwidth + 1]) {
+                                        const float ax = ul - fx0, ay = vl - fy0;
+                                        const float m00 = (float)g.m_S[lp] * g.iscale, m10 = (float)g.m_S[lp + 1] * g.iscale;
+                                        const float m01 = (float)g.m_S[lp + a.fwidth] * g.iscale;
+                                        const float m11 = (float)g.m_S[lp + a.fwidth + 1] * g.iscale;
+                                        const float dx0 = m10 - m00, dx1 = m11 - m01, dy0 = m01 - m00;
+                                        const float top = fmaf(ax, dx0, m00), bot = fmaf(ax, dx1, m01);
+                                        const float Im = fmaf(ay, bot - top, top);
+                                        const float gx = fmaf(ay, dx1 - dx0, dx0);
+                                        const float gy = fmaf(ax, (m11 - m10) - dy0, dy0);
+                                        const float res = (float)g.f_S[px] * g.iscale - Im;
+                                        if (fabsf(res) > g.r_max) {
+                                            pcls = 2;
+                                        } else {
+                                            const float a0 = (gx * g.fxl) * iz, a1 = (gy * g.fyl) * iz;
+                                            const float a2 = -((a0 * qx + a1 * qy) * iz);
+                                            float aw[3];
+                                            aw[0] = dot3(a.Eref[0], a.Eref[4], a.Eref[8], a0, a1, a2);
+                                            aw[1] = dot3(a.Eref[1], a.Eref[5], a.Eref[9], a0, a1, a2);
+                                            aw[2] = dot3(a.Eref[2], a.Eref[6], a.Eref[10], a0, a1, a2);
+                                            cross3(Pw, aw, Jp);
+                                            Jp[3] = aw[0];
+                                            Jp[4] = aw[1];
+                                            Jp[5] = aw[2];
+                                            bool in = true;
+                                            for (int k = 0; k < 6; ++k) in = in && fabsf(Jp[k]) < 2048.0f;
+                                            if (in) {
+                                                pcls = 0;
+                                                rp = res;
+                                            }
+                                        }
+                                    }
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        // the ballots are taken by the whole wave
+        const unsigned long long inl = __ballot(cls == 0), pinl = __ballot(pcls == 0);
+        cnt[0] += __popcll(inl);
+        cnt[1] += __popcll(__ballot(cls == 1));
+        cnt[2] += __popcll(__ballot(cls == 2));
+        cnt[3] += __popcll(__ballot(cls == 3));
+        cnt[4] += __popcll(pinl);
+        cnt[5] += __popcll(__ballot(pcls == 1));
+        cnt[6] += __popcll(__ballot(pcls == 2));
+        cnt[7] += __popcll(__ballot(pcls == 3));
+        if (inl) {  // wave-uniform; a lane that is no inlier adds zeros
+            if (cls != 0) {
+                for (int k = 0; k < 6; ++k) J[k] = 0.0f;
+                r = 0.0f;
+            }
+            int w = 0;
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+#pragma unroll
+                for (int j = i; j < 6; ++j) acc[w++] += icp_fix(J[i], J[j]);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) acc[21 + i] += icp_fix(J[i], r);
+            acc[27] += icp_fix(r, r);
+        }
+        if (pinl) {
+            if (pcls != 0) {
+                for (int k = 0; k < 6; ++k) Jp[k] = 0.0f;
+                rp = 0.0f;
+            }
+            int w = kIcpSums;
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+#pragma unroll
+                for (int j = i; j < 6; ++j) acc[w++] += rgbd_fix(Jp[i], Jp[j]);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) acc[kIcpSums + 21 + i] += rgbd_fix(Jp[i], rp);
+            acc[kIcpSums + 27] += rgbd_fix(rp, rp);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 2 * kIcpSums; ++k) {
+        long long s = acc[k];
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        if (lane == 0) red[wave][(k / kIcpSums) * kIcpWords + (k % kIcpSums)] = s;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) red[wave][(k / 4) * kIcpWords + kIcpSums + (k % 4)] = (long long)cnt[k];
+    }
+    __syncthreads();
+    if (tid < kRgbdWords) {
+        const long long s = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+        if (s) atomicAdd(reinterpret_cast<unsigned long long*>(a.words) + tid, (unsigned long long)s);
+    }
+}
+
+hipError_t launch_rgbd_system(const RgbdArgs& a, hipStream_t s) {
+    const int nx = (a.icp.fwidth - 1) / a.icp.stride + 1, ny = (a.icp.fheight - 1) / a.icp.stride + 1;  // visited pixels
+    const int tiles_x = (nx + 15) / 16, ntiles = tiles_x * ((ny + 15) / 16);
+    hipLaunchKernelGGL(k_rgbd_system, dim3(ntiles < kRgbdGrid ? ntiles : kRgbdGrid), dim3(256), 0, s, a, tiles_x, ntiles);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
 // Z-sharded raycast.  The march of march_ray is sequential along the ray
 // (sticky quarter step, refinement from the previous sample), so it is split into steps
 // that every rank of the group runs on its own planes, with an all-gather of one 8-byte

@@ -134,8 +134,19 @@ class FrameLevel(C.Structure):
                 ("vertex", C.c_void_p), ("normal", C.c_void_p), ("flags", C.c_void_p)]
 
 
+class IntensityLevel(C.Structure):
+    """semtsdf_intensity_level: width and height are written by the library; S and valid are required."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("S", C.c_void_p), ("valid", C.c_void_p)]
+
+
+class RgbdIn(C.Structure):
+    """semtsdf_rgbd_in: S and valid of one level of the frame's and the model's intensity pyramids."""
+    _fields_ = [("f_S", C.c_void_p), ("f_valid", C.c_void_p), ("m_S", C.c_void_p), ("m_valid", C.c_void_p)]
+
+
 PYRAMID_MAX_LEVELS = 4
 ICP_WORDS = 32
+RGBD_WORDS = 64
 MAP_HIT = 0x1
 MAP_NORMAL = 0x2
 MAP_NAMES = ("t", "point", "normal", "label", "votes", "flags")
@@ -221,6 +232,12 @@ SIGNATURES = {
     "semtsdf_icp_system_level": (_I, [_P, C.POINTER(IcpIn), C.c_int32, C.c_int32, _P, _P, _F, _F, C.c_int32, _P, _P]),
     "semtsdf_icp_system_level_dev": (_I, [_P, C.POINTER(IcpIn), C.c_int32, C.c_int32, _P, _P, _F, _F, C.c_int32, _P,
                                           _P]),
+    "semtsdf_intensity_pyramid": (_I, [_P, _P, _P, _I, C.POINTER(IntensityLevel), _P]),
+    "semtsdf_intensity_pyramid_dev": (_I, [_P, _P, _P, _I, C.POINTER(IntensityLevel), _P]),
+    "semtsdf_rgbd_system_level": (_I, [_P, C.POINTER(IcpIn), C.POINTER(RgbdIn), C.c_int32, _P, _P, _F, _F, _F, C.c_int32,
+                                       _P, _P]),
+    "semtsdf_rgbd_system_level_dev": (_I, [_P, C.POINTER(IcpIn), C.POINTER(RgbdIn), C.c_int32, _P, _P, _F, _F, _F,
+                                           C.c_int32, _P, _P]),
     "semtsdf_shard_ray_begin": (_I, [_P, _I, _P, _P, _I, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "semtsdf_shard_ray_step": (_I, [_P, _I, _P, _P, _P]),
     "semtsdf_shard_render_finish": (_I, [_P, _P, _P, _P, _P]),

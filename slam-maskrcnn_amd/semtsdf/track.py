@@ -6,7 +6,10 @@ reference view (semtsdf_render_maps_dev), the frame maps of the depth image
 (semtsdf_icp_system_dev).  This module is the host side, NumPy float64 like pose.py: it scales the
 words back, solves the 6 x 6 system and moves the pose.  track_pyramid runs the same loop coarse to
 fine on the depth pyramid (include/semtsdf.h, "depth pyramid": semtsdf_frame_pyramid_dev,
-semtsdf_icp_system_level_dev) against the one full-resolution render of the model.
+semtsdf_icp_system_level_dev) against the one full-resolution render of the model, and track_rgbd
+adds a photometric term between the frame's colour image and the model's colour render
+(include/semtsdf.h, "RGB-D tracking": semtsdf_intensity_pyramid_dev, semtsdf_rgbd_system_level_dev),
+whose row J = (Pw x aw, aw) follows the same convention: r - J xi is the intensity residual after the step.
 
 Conventions.  E is the integrate's extrinsic: volume frame to camera, so C2W = E^-1 is the camera's
 pose in the volume frame.  A step is a twist xi = (omega, v) of the volume frame:
@@ -253,6 +256,131 @@ def track_pyramid(vol, depth, E_ref, E0, schedule=PYRAMID_SCHEDULE, radius=3, si
             b.free()
 
 
+PHOTO_SCALE = 2.0 ** -20    # one unit of the photometric sums
+PHOTO_COUNT_NAMES = ("inliers", "far", "outlier", "none")
+PHOTO_WEIGHT = 0.02         # metres per unit of intensity (the sweep that chose it)
+R_MAX = 0.25                # the gate on the intensity residual, intensities in [0, 1)
+
+
+def rgbd_system_from_words(words):
+    """Two (A, b, r2, counts) tuples of the 64 int64 words: the point-to-plane system as
+    system_from_words returns it (scale 2^-32, metres) and the photometric one (scale 2^-20, units of
+    intensity; counts inliers, far, outlier, none)."""
+    w = np.asarray(words, np.int64).reshape(L.RGBD_WORDS)
+    p = w[L.ICP_WORDS:]
+    A = np.zeros((6, 6), np.float64)
+    A[np.triu_indices(6)] = p[:21].astype(np.float64) * PHOTO_SCALE
+    A = A + np.triu(A, 1).T
+    b = p[21:27].astype(np.float64) * PHOTO_SCALE
+    counts = {n: int(p[28 + k]) for k, n in enumerate(PHOTO_COUNT_NAMES)}
+    return system_from_words(w[:L.ICP_WORDS]), (A, b, float(p[27]) * PHOTO_SCALE, counts)
+
+
+def rgbd_loop(system, dims, E0, schedule=PYRAMID_SCHEDULE, photo_weight=PHOTO_WEIGHT, r_max=R_MAX, stride=1,
+              min_inliers=None, eps=STEP_EPS):
+    """pyramid_loop with the photometric term: system(level, E_cur, dist_max, cos_min, r_max) -> 64
+    int64 words.  Each iteration solves (A_g + w^2 A_p) xi = b_g + w^2 b_p with w = photo_weight; a
+    photometric system with fewer than the level's min_inliers inliers is left out of that iteration
+    (photo_used False in its log entry).  The step, the stop rule and TrackingLost (on the geometric
+    inliers alone) are track_loop's.  Log entries are pyramid_loop's plus photo_inliers, photo_rms
+    (intensity units, before the step) and photo_used."""
+    E = np.asarray(E0, np.float32).reshape(4, 4).copy()
+    w2 = float(photo_weight) ** 2
+    log = []
+    for level, iters, dist_max, cos_min in schedule:
+        level = int(level)
+        w, h = dims[level]
+        need = default_min_inliers(w, h, int(stride)) if min_inliers is None else min_inliers
+        for it in range(int(iters)):
+            (A, b, r2, counts), (Ap, bp, rp2, pc) = rgbd_system_from_words(system(level, E, dist_max, cos_min, r_max))
+            n, m = counts["inliers"], pc["inliers"]
+            used = m >= need and w2 > 0.0
+            entry = dict(counts, iter=it, rms=math.sqrt(r2 / n) if n else float("nan"), step=float("nan"), level=level,
+                         photo_inliers=m, photo_rms=math.sqrt(rp2 / m) if m else float("nan"), photo_used=used)
+            log.append(entry)
+            if n < need:
+                raise TrackingLost(f"level {level}: iteration {it}: {n} inliers, fewer than {need}", E, log)
+            try:
+                xi = solve_step(A + w2 * Ap, b + w2 * bp) if used else solve_step(A, b)
+            except np.linalg.LinAlgError as e:
+                raise TrackingLost(f"level {level}: iteration {it}: {e}", E, log) from e
+            entry["step"] = float(np.linalg.norm(xi))
+            E = se3_apply(xi, E)
+            if entry["step"] < eps:
+                break
+    return E, log
+
+
+def track_rgbd(vol, depth, rgb, E_ref, E0, schedule=PYRAMID_SCHEDULE, photo_weight=PHOTO_WEIGHT, r_max=R_MAX, radius=3,
+               sigma_r=0.05, band=None, stride=1, min_weight=1, min_inliers=None, eps=STEP_EPS):
+    """track_pyramid with a photometric term between the frame's colour image `rgb` (u8 [H, W, 3]) and
+    the colour render of the model.  Once: the model maps and the colour raycast at
+    pose_camera(Kinv, E_ref), the depth pyramid, and the intensity pyramids of the frame and of the
+    render (valid where the model flags are 3); then per iteration one launch
+    (Volume.rgbd_system_level_dev) and a 512-byte read-back.  Returns (E, log) as rgbd_loop does, and
+    raises TrackingLost like it."""
+    from .maps import pose_camera
+    from .volume import DeviceBuffer
+
+    d = np.ascontiguousarray(depth, dtype=np.uint16)
+    c = np.ascontiguousarray(rgb, dtype=np.uint8)
+    n = vol.W * vol.H
+    if d.size != n or c.size != 3 * n:
+        raise ValueError(f"depth must be {vol.H}x{vol.W} u16 and rgb {vol.H}x{vol.W}x3 u8")
+    schedule = tuple(tuple(s) for s in schedule)
+    if not schedule or min(int(s[0]) for s in schedule) < 0:
+        raise ValueError("schedule: (level, iterations, dist_max, cos_min) entries with level >= 0")
+    nlevels = max(int(s[0]) for s in schedule) + 1
+    geo = vol.frame_levels(nlevels)
+    E_ref = L.f32(E_ref, 16)
+    s2w, cam = pose_camera(list(vol.params.Kinv), E_ref)
+    stream = C.c_void_p(vol.stream)
+    sizes = {"depth": 2 * n, "rgb": 3 * n, "m_rgb": 3 * n, "m_point": 12 * n, "m_normal": 12 * n, "m_flags": n,
+             "m_valid": n, "words": 8 * L.RGBD_WORDS}
+    for l, g in enumerate(geo):
+        m = g["width"] * g["height"]
+        sizes.update({f"z{l}": 4 * m, f"vertex{l}": 12 * m, f"normal{l}": 12 * m, f"flags{l}": m,
+                      f"fS{l}": 4 * m, f"fV{l}": m, f"mS{l}": 4 * m, f"mV{l}": m})
+    bufs = {}
+    try:
+        for k, size in sizes.items():
+            bufs[k] = DeviceBuffer(size)
+        vol.render_maps_dev(s2w, cam, int(min_weight), point=bufs["m_point"].ptr, normal=bufs["m_normal"].ptr,
+                            flags=bufs["m_flags"].ptr)
+        vol.raycast_dev(s2w, cam, L.RENDER_COLOR, bufs["m_rgb"].ptr, stream=stream)
+        m_flags = np.zeros(n, np.uint8)   # the one read-back before the loop: valid = (m_flags & 3) == 3
+        bufs["m_flags"].download(m_flags, stream)
+        vol.sync()
+        m_valid = np.ascontiguousarray((m_flags & 3) == 3, dtype=np.uint8)
+        bufs["m_valid"].upload(m_valid, stream)
+        bufs["depth"].upload(d, stream)
+        bufs["rgb"].upload(c, stream)
+        vol.frame_pyramid_dev(bufs["depth"].ptr, [{k: bufs[f"{k}{l}"].ptr for k in ("z", "vertex", "normal", "flags")}
+                                                  for l in range(nlevels)], radius, sigma_r, band)
+        vol.intensity_pyramid_dev(bufs["rgb"].ptr, None, [{"S": bufs[f"fS{l}"].ptr, "valid": bufs[f"fV{l}"].ptr}
+                                                          for l in range(nlevels)])
+        vol.intensity_pyramid_dev(bufs["m_rgb"].ptr, bufs["m_valid"].ptr,
+                                  [{"S": bufs[f"mS{l}"].ptr, "valid": bufs[f"mV{l}"].ptr} for l in range(nlevels)])
+        model = [bufs[k].ptr for k in ("m_point", "m_normal", "m_flags")]
+        words = np.zeros(L.RGBD_WORDS, np.int64)
+
+        def system(level, E, dist_max, cos_min, r_max):
+            frame = [bufs[f"{k}{level}"].ptr for k in ("vertex", "normal", "flags")]
+            photo = [bufs[f"{k}{level}"].ptr for k in ("fS", "fV", "mS", "mV")]
+            vol.rgbd_system_level_dev(frame + model, photo, level, E_ref, E, dist_max, cos_min, r_max, stride,
+                                      bufs["words"].ptr)
+            bufs["words"].download(words, stream)
+            vol.sync()
+            return words
+
+        dims = [(g["width"], g["height"]) for g in geo]
+        return rgbd_loop(system, dims, E0, schedule, photo_weight, r_max, stride, min_inliers, eps)
+    finally:
+        vol.sync()
+        for b in bufs.values():
+            b.free()
+
+
 def pose_errors(E, E_true):
     """(translation error in metres, rotation angle in radians) between two extrinsics, measured
     on the camera poses C2W = E^-1."""
@@ -264,4 +392,5 @@ def pose_errors(E, E_true):
 
 
 __all__ = ["TrackingLost", "system_from_words", "solve_step", "se3_exp", "se3_apply", "track_loop", "track",
-           "pose_errors", "default_min_inliers", "STEP_EPS", "PYRAMID_SCHEDULE", "pyramid_loop", "track_pyramid"]
+           "pose_errors", "default_min_inliers", "STEP_EPS", "PYRAMID_SCHEDULE", "pyramid_loop", "track_pyramid",
+           "rgbd_system_from_words", "rgbd_loop", "track_rgbd", "PHOTO_WEIGHT", "R_MAX"]

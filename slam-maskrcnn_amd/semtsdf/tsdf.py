@@ -266,22 +266,28 @@ class TSDF:
         return self.vol.render_maps(s2w, c, min_weight, want)
 
     # ------------------------------------------------------------------ tracking
-    def track(self, depth, guess=None, pyramid=False, **kw):
+    def track(self, depth, guess=None, pyramid=False, rgb=None, **kw):
         """The W2C extrinsic of a depth image, tracked against the fused model by point-to-plane ICP
         (semtsdf.track.track; **kw are its options): the pose to hand to parse_frame for this frame.
         `guess` is a W2C extrinsic as parse_frame takes it, by default the last fused frame's; the
         model is viewed from it.  pyramid=True tracks coarse to fine on the filtered depth pyramid
         (semtsdf.track.track_pyramid and its options): for noisy depth or a guess further off.
+        `rgb` (u8 [H, W, 3], the frame's colour image) adds the photometric term against the
+        model's colour render (semtsdf.track.track_rgbd and its options, coarse to fine): for
+        walls, floors and table tops, where depth alone leaves the in-plane motion free.
         Raises semtsdf.track.TrackingLost when too few pixels match.  The per-iteration log is kept
         in `last_track`."""
-        from .track import track, track_pyramid
+        from .track import track, track_pyramid, track_rgbd
 
         if guess is None:
             guess = self.last_extrinsic
         if guess is None or self.vol is None:
             raise ValueError("nothing fused yet: no model to track against")
         E0 = P.relative_pose(guess, self.init_extrinsic_inv)
-        E, self.last_track = (track_pyramid if pyramid else track)(self.vol, depth, E0, E0, **kw)
+        if rgb is not None:
+            E, self.last_track = track_rgbd(self.vol, depth, rgb, E0, E0, **kw)
+        else:
+            E, self.last_track = (track_pyramid if pyramid else track)(self.vol, depth, E0, E0, **kw)
         return E.astype(np.float64) @ np.linalg.inv(np.asarray(self.init_extrinsic_inv, np.float64))
 
     def orbit(self, n: int, out_dir: str | None = None, mode: str = "label", step: float = 0.01, callback=None):

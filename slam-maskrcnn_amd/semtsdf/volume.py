@@ -414,6 +414,79 @@ class Volume:
             L.ptr(er), L.ptr(ec), float(dist_max), float(cos_min), int(stride),
             C.c_void_p(words_ptr) if words_ptr else None, stream))
 
+    # ---- RGB-D tracking (semtsdf/track.py's track_rgbd drives these)
+    def intensity_pyramid(self, rgb, valid=None, nlevels: int = 3) -> list:
+        """The intensity pyramid of a u8 colour image [H, W, 3] (semtsdf_intensity_pyramid): one dict
+        per level with width, height, S (u32 [h, w], the integer sums; the intensity is
+        S * 2^-(14 + 2 l)) and valid (u8 [h, w]).  `valid` u8 [H, W], nonzero = valid; None: all valid."""
+        c = np.ascontiguousarray(rgb, dtype=np.uint8)
+        if c.size != self.W * self.H * 3:
+            raise ValueError(f"rgb must be {self.H}x{self.W}x3 u8")
+        m = None
+        if valid is not None:
+            m = np.ascontiguousarray(valid, dtype=np.uint8)
+            if m.size != self.W * self.H:
+                raise ValueError(f"valid must be {self.H}x{self.W} u8")
+        nl = int(nlevels)
+        lv = (L.IntensityLevel * max(nl, L.PYRAMID_MAX_LEVELS))()
+        out = []
+        for l in range(max(0, min(nl, L.PYRAMID_MAX_LEVELS))):  # the library refuses a bad count
+            h, w = self.H >> l, self.W >> l
+            out.append({"width": w, "height": h, "S": np.zeros((h, w), np.uint32), "valid": np.zeros((h, w), np.uint8)})
+            lv[l].S = out[l]["S"].ctypes.data
+            lv[l].valid = out[l]["valid"].ctypes.data
+        L.check(L.load().semtsdf_intensity_pyramid(self._h, L.ptr(c), L.ptr(m), nl, lv, None))
+        return out
+
+    def intensity_pyramid_dev(self, rgb_ptr: int, valid_ptr, levels, stream=None) -> list:
+        """intensity_pyramid from and into device buffers, one launch, asynchronous on `stream`:
+        `levels` holds one dict per level with the raw device pointers "S" and "valid"; valid_ptr may
+        be None.  Returns the levels' width and height."""
+        nl = len(levels)
+        lv = (L.IntensityLevel * max(nl, L.PYRAMID_MAX_LEVELS))()
+        for o, v in zip(levels, lv):
+            v.S = int(o["S"]) if o.get("S") else None
+            v.valid = int(o["valid"]) if o.get("valid") else None
+        L.check(L.load().semtsdf_intensity_pyramid_dev(self._h, C.c_void_p(rgb_ptr) if rgb_ptr else None,
+                                                       C.c_void_p(valid_ptr) if valid_ptr else None, nl, lv, stream))
+        return [{"width": int(v.width), "height": int(v.height)} for v in lv[:nl]]
+
+    def rgbd_system_level(self, frame: dict, model: dict, f_int: dict, m_int: dict, level: int, E_ref, E_cur,
+                          dist_max: float = 0.1, cos_min: float = 0.8, r_max: float = 0.1, stride: int = 1) -> np.ndarray:
+        """The 64 int64 words of one RGB-D iteration on pyramid level `level`
+        (semtsdf_rgbd_system_level) from host arrays: `frame` and `model` as icp_system_level takes
+        them (the frame maps of that level), `f_int` and `m_int` that level of intensity_pyramid of the
+        frame's colour image and of the model's colour render (dicts with S and valid)."""
+        fh, fw = self.H >> int(level), self.W >> int(level)
+        n = self.W * self.H
+        arrs = [np.ascontiguousarray(frame["vertex"], np.float32), np.ascontiguousarray(frame["normal"], np.float32),
+                np.ascontiguousarray(frame["flags"], np.uint8), np.ascontiguousarray(model["point"], np.float32),
+                np.ascontiguousarray(model["normal"], np.float32), np.ascontiguousarray(model["flags"], np.uint8)]
+        ints = [np.ascontiguousarray(f_int["S"], np.uint32), np.ascontiguousarray(f_int["valid"], np.uint8),
+                np.ascontiguousarray(m_int["S"], np.uint32), np.ascontiguousarray(m_int["valid"], np.uint8)]
+        for a, size in zip(arrs + ints, (fw * fh * 3, fw * fh * 3, fw * fh, n * 3, n * 3, n) + (fw * fh,) * 4):
+            if a.size != size:
+                raise ValueError(f"frame maps and intensities must be {fh}x{fw}, model maps {self.H}x{self.W}")
+        words = np.zeros(L.RGBD_WORDS, np.int64)
+        er, ec = L.f32(E_ref, 16), L.f32(E_cur, 16)
+        L.check(L.load().semtsdf_rgbd_system_level(
+            self._h, C.byref(L.IcpIn(*[a.ctypes.data for a in arrs])), C.byref(L.RgbdIn(*[a.ctypes.data for a in ints])),
+            int(level), L.ptr(er), L.ptr(ec), float(dist_max), float(cos_min), float(r_max), int(stride), L.ptr(words),
+            None))
+        return words
+
+    def rgbd_system_level_dev(self, pointers, photo, level: int, E_ref, E_cur, dist_max, cos_min, r_max, stride,
+                              words_ptr: int, stream=None):
+        """rgbd_system_level on device buffers: `pointers` as icp_system_level_dev takes them, `photo`
+        the four raw pointers in semtsdf_rgbd_in order (frame S, valid; model S, valid), `words_ptr`
+        64 int64 on the device; asynchronous on `stream`, nothing is read back."""
+        er, ec = L.f32(E_ref, 16), L.f32(E_cur, 16)
+        L.check(L.load().semtsdf_rgbd_system_level_dev(
+            self._h, C.byref(L.IcpIn(*[int(p) if p else None for p in pointers])),
+            C.byref(L.RgbdIn(*[int(p) if p else None for p in photo])), int(level), L.ptr(er), L.ptr(ec),
+            float(dist_max), float(cos_min), float(r_max), int(stride), C.c_void_p(words_ptr) if words_ptr else None,
+            stream))
+
     # ---- state transfer (reference layouts)
     def download(self, sdf=True, wt=True, color=True, hist=False, cls=False):
         n = self.nvox
