@@ -177,6 +177,27 @@ int semtsdf_set_state(semtsdf_vol* v, uint32_t n_obs, int32_t num_objs);
 void* semtsdf_get_stream(const semtsdf_vol* v);
 /* sdf := mu (metres, tsdf.cu:243-244), weight/colour/histogram := 0, n_obs = num_objs = 0. */
 int semtsdf_reset(semtsdf_vol* v, void* stream);
+/* Move the volume by whole 8^3 bricks so that it follows the camera (no reference counterpart).
+ * shift = (sx, sy, sz) in voxels, each a multiple of 8 with |s| < 2^20.  Afterwards the voxel at
+ * index i holds what the voxel at i + s held -- sdf, weight, colour, all 32 histogram bins, the
+ * label vote -- in the storage form it had; a voxel whose source i + s lies outside [0, dim) on any
+ * axis holds what semtsdf_reset leaves (sdf = mu, everything else 0).  The placement moves with it,
+ * rounded once from double: vol_start[a] = (float)((double)vol_start[a] + (double)s[a] *
+ * (double)voxel[a]), vol_end likewise; semtsdf_get_params returns it and every later call uses it.
+ * Poses are relative to frame 0 (E = W2C_k * W2C_0^-1), not to vol_start, so they stay valid.
+ * voxel, mu, dim, n_obs, num_objs, the weight bound, the storage forms and the dropped-vote counter
+ * do not change.  The empty-space maps are rebuilt by the next march and the steady flags cleared,
+ * as after semtsdf_upload.  |s[a]| >= dim[a] is legal: the whole volume becomes the reset state and
+ * the counters keep their values.  (0, 0, 0) does nothing and returns SEMTSDF_OK.
+ * The call orders itself after the work queued on the handle (as semtsdf_reset and semtsdf_upload
+ * do), runs on `stream` and synchronises before it returns.  It holds at most 16 bytes per stored
+ * voxel of extra device memory while it runs (counted in device_bytes, released before return).
+ * Errors, decided before any device work: a NULL argument, a component that is not a multiple of
+ * 8 or with |s| >= 2^20, a new placement that is not finite: SEMTSDF_ERR_INVALID; a Z-sharded
+ * handle: SEMTSDF_ERR_STATE.  SEMTSDF_ERR_OOM from the first allocation leaves the volume as it
+ * was; a failure later in the call leaves voxel contents that only semtsdf_reset or a full
+ * semtsdf_upload make defined again. */
+int semtsdf_shift(semtsdf_vol* v, const int32_t shift[3], void* stream);
 
 /* ---- integrate (a4) ------------------------------------------------------------------
  * One frame into the volume: E = extrinsic * init_extrinsic_inv (row-major 4x4 f32,

@@ -1181,6 +1181,101 @@ int semtsdf_reset(semtsdf_vol* v, void* stream) {
     return SEMTSDF_OK;
 }
 
+// The volume follows the camera: every per-voxel array moved by whole bricks inside HBM (DESIGN.md
+// "Shifting the volume").  No array is moved in place: the 4-byte arrays take turns through one
+// spare of 4 * nvox bytes (shifted into it, then the two pointers change roles), each histogram
+// plane is shifted into the spare and copied back, and the two arrays of another size (u16
+// weights, wide colour) go into a fresh buffer that replaces them (pool.swap, as widen_weights).
+int semtsdf_shift(semtsdf_vol* v, const int32_t shift[3], void* stream) {
+    if (!v || !shift) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
+    for (int a = 0; a < 3; ++a) {  // the shift alone first: refused without a look at the handle
+        if (shift[a] % kShiftBrick)
+            return fail(SEMTSDF_ERR_INVALID, "shift[%d]=%d is not a multiple of %d voxels", a, shift[a], kShiftBrick);
+        if (shift[a] <= -kShiftLimit || shift[a] >= kShiftLimit)
+            return fail(SEMTSDF_ERR_INVALID, "shift[%d]=%d out of range (|shift| < 2^20)", a, shift[a]);
+    }
+    float start[3], end[3];
+    for (int a = 0; a < 3; ++a) {
+        // the new placement, rounded once from double
+        start[a] = (float)((double)v->p.vol_start[a] + (double)shift[a] * (double)v->p.voxel[a]);
+        end[a] = (float)((double)v->p.vol_end[a] + (double)shift[a] * (double)v->p.voxel[a]);
+        if (!std::isfinite(start[a]) || !std::isfinite(end[a]))
+            return fail(SEMTSDF_ERR_INVALID, "shift[%d]=%d leaves no finite placement", a, shift[a]);
+    }
+    if (v->g.nshards > 1)
+        return fail(SEMTSDF_ERR_STATE, "semtsdf_shift: a Z-sharded handle cannot be shifted (its halo planes would "
+                    "need an exchange)");
+    if (!shift[0] && !shift[1] && !shift[2]) return SEMTSDF_OK;
+    HIPC(hipSetDevice(v->device));
+    hipStream_t s = pick(v, stream);
+    if (int rc = after_maps(v, s)) return rc;
+    // everything queued on the handle's own streams reads or writes the arrays about to move
+    if (s != v->stream) HIPC(hipStreamSynchronize(v->stream));
+    if (v->prep_stream) HIPC(hipStreamSynchronize(v->prep_stream));
+    // non-temporal loads and stores: every byte is touched once (3.5 % faster at 512^3,
+    // profiles/shift_time.txt); SEMTSDF_SHIFT_NT=0 selects plain accesses (timing probes only)
+    static const char* nt_env = getenv("SEMTSDF_SHIFT_NT");
+    const bool nt = !nt_env || atoi(nt_env) != 0;
+    const VolGeom& g = v->g;
+    const size_t n = g.nvox;
+    const ShiftGeom sg{g.dimx, g.dimy, g.lz, (int)g.nuy, (int)g.nuz * 8, shift[0], shift[1], shift[2]};
+    // derived state first, as semtsdf_upload: 0 = unknown is always safe
+    v->maps_stale = true;
+    HIPC(hipMemsetAsync(v->b.sflag, 0, n / 32 + 1, s));
+    uint32_t mu_bits;
+    memcpy(&mu_bits, &g.mu, sizeof(mu_bits));
+    // the arrays of a size of their own
+    auto replace = [&](void** slot, int bpv) {
+        return v->pool.swap(slot, n * (size_t)bpv, [&](void* fresh) {
+            HIPC(launch_shift_lines(sg, *slot, fresh, n, bpv, 0u, nt, s));
+            HIPC(hipStreamSynchronize(s));
+            return SEMTSDF_OK;
+        });
+    };
+    // The largest request first: when it is refused nothing has moved yet.  At most 16 * nvox bytes
+    // are held beside the volume at any time (wide colour alone; then the spare and 2 * nvox).
+    if (v->color_wide)
+        if (int rc = replace(&v->b.color, 16)) return rc;
+    // the 4-byte arrays, through one spare
+    void* spare = nullptr;
+    if (int rc = v->pool.alloc(&spare, n * 4)) return rc;
+    auto release_spare = [&](int rc) { v->pool.release(spare); return rc; };
+    if (!v->wt_wide)
+        if (int rc = replace(&v->b.wt, 2)) return release_spare(rc);
+    auto rotate = [&](void** slot, uint32_t fill) {
+        if (!*slot) return SEMTSDF_OK;
+        HIPC(launch_shift_lines(sg, *slot, spare, n, 4, fill, nt, s));
+        std::swap(*slot, spare);
+        return SEMTSDF_OK;
+    };
+    int rc = rotate((void**)&v->b.sdf, mu_bits);
+    if (!rc && v->wt_wide) rc = rotate(&v->b.wt, 0u);
+    if (!rc && !v->color_wide) rc = rotate(&v->b.color, 0u);
+    if (!rc) rc = rotate((void**)&v->b.hmask, 0u);
+    if (!rc) rc = rotate((void**)&v->b.cls, 0u);
+    if (!rc) rc = rotate((void**)&v->b.cls_cnt, 0u);
+    if (rc) { (void)hipStreamSynchronize(s); return release_spare(rc); }
+    if (v->b.hist) {
+        for (int k = 0; k < kMaxObjects; ++k) {
+            uint32_t* plane = v->b.hist + (size_t)k * n;
+            hipError_t e = launch_shift_lines(sg, plane, spare, n, 4, 0u, nt, s);
+            if (e == hipSuccess) e = launch_copy_f4(spare, plane, n / 4, s);
+            if (e != hipSuccess) {
+                (void)hipStreamSynchronize(s);
+                return release_spare(fail(SEMTSDF_ERR_HIP, "shift of histogram plane %d: %s", k, hipGetErrorString(e)));
+            }
+        }
+    }
+    for (int a = 0; a < 3; ++a) {
+        v->p.vol_start[a] = v->g.start[a] = start[a];
+        v->p.vol_end[a] = v->g.end[a] = end[a];
+    }
+    const hipError_t e = hipStreamSynchronize(s);
+    release_spare(0);
+    if (e != hipSuccess) return fail(SEMTSDF_ERR_HIP, "semtsdf_shift: %s", hipGetErrorString(e));
+    return SEMTSDF_OK;
+}
+
 // The observation count of a semantic volume follows its integrated frames, as in the
 // reference, where every integrated frame advances n_obs_ (tsdf.cu:218-220) and the first one
 // sets num_objs = max(mask) + 1 (tsdf.cu:463-468): the split calls (associate, then integrate)

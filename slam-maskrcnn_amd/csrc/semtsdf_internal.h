@@ -5,6 +5,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "semtsdf_shift.h"
+
 namespace semtsdf {
 
 constexpr int kMaxObjects = 32;
@@ -451,6 +453,11 @@ hipError_t launch_vox_chunk(const void* src, void* dst, bool to_ref, const VolGe
                             hipStream_t s, bool dev_u16 = false);  // dev_u16: the device array holds uint16_t
 hipError_t launch_weight_widen(const uint16_t* narrow, int32_t* wide, uint64_t nvox, hipStream_t s);  // u16 -> i32
 hipError_t launch_color_widen(const uint8_t* narrow, int32_t* wide, uint64_t nvox, hipStream_t s);  // u8x4 -> i32x4
+// semtsdf_shift: the nvox stored voxels of one array (bytes_per_voxel 2, 4 or 16) gathered from src into
+// another buffer dst by the rule of semtsdf_shift.h; voxels without a source take `fill` (a 32-bit
+// pattern; its low half for 2-byte voxels).  One thread per 16-B vector, uncapped grid.
+hipError_t launch_shift_lines(const ShiftGeom& sg, const void* src, void* dst, uint64_t nvox, int bytes_per_voxel,
+                              uint32_t fill, bool nontemporal, hipStream_t s);
 hipError_t launch_color_chunk(const void* src, void* dst, bool to_ref, bool ref_i32, bool dev_i32, const VolGeom& g,
                               uint64_t v0, uint64_t nv, hipStream_t s);
 hipError_t launch_integrate(const IntegrateArgs& a, hipStream_t s, hipEvent_t e0 = nullptr,

@@ -28,6 +28,7 @@
 #include <stdlib.h>
 #include "semtsdf_internal.h"
 #include "semtsdf_libm.h"
+#include "semtsdf_shift.h"
 #include "semtsdf_steps.h"
 
 namespace semtsdf {
@@ -4760,6 +4761,79 @@ hipError_t launch_color_widen(const uint8_t* narrow, int32_t* wide, uint64_t nvo
     if (blocks > kWidenBlocks) blocks = kWidenBlocks;
     hipLaunchKernelGGL(k_color_widen, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(narrow),
                        reinterpret_cast<int4*>(wide), nvox);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------
+// semtsdf_shift: one per-voxel array (or histogram plane) moved by whole bricks, from src into
+// another buffer dst.  A line-granular gather by the rule of semtsdf_shift.h: one thread per
+// 16-B vector of the destination, consecutive lanes on consecutive addresses of both sides (a
+// voxel keeps its place inside its line).  BPV = bytes per voxel: 2 (u16 weights), 4, 16 (wide
+// colour); fill = the reset value as a 32-bit pattern (its low half for BPV 2).  Lines whose
+// voxels are all kept are copied whole; the ragged ones (last y-group, last z-tile, and their
+// images under the shift) are masked per voxel.  The grid covers every vector once (no cap, no
+// loop: the shape k_copy_f4 reaches the copy rate with).  NT: non-temporal accesses
+// (tools/shift_time.py measures both).
+// ------------------------------------------------------------------------------------
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+template <int BPV, bool NT>
+__global__ __launch_bounds__(256) void k_shift_lines(ShiftGeom sg, const u32x4* __restrict__ src,
+                                                     u32x4* __restrict__ dst, uint64_t nvec, uint32_t fill) {
+    constexpr unsigned kVecPerLine = kLineVoxels * BPV / 16;  // 4, 8, 32
+    constexpr int kVoxPerVec = 16 / BPV;                      // 8, 4, 1
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= nvec) return;
+    const uint32_t line = (uint32_t)(i / kVecPerLine), e = (uint32_t)(i % kVecPerLine);
+    const ShiftLine c = shift_line_coords(sg, line);
+    const int64_t sl = shift_source_line(sg, c);
+    const uint32_t f = BPV == 2 ? (fill & 0xFFFFu) * 0x10001u : fill;
+    u32x4 val = {f, f, f, f};
+    if (sl >= 0) {
+        const u32x4* p = src + (uint64_t)sl * kVecPerLine + e;
+        val = NT ? __builtin_nontemporal_load(p) : *p;
+        if (!shift_line_whole(sg, c)) {
+            const int w0 = (int)e * kVoxPerVec;  // first voxel of the vector inside its line
+            if (BPV == 16) {
+                if (!shift_voxel_kept(sg, c, w0)) val = u32x4{f, f, f, f};
+            } else if (BPV == 4) {
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+                    if (!shift_voxel_kept(sg, c, w0 + m)) val[m] = f;
+            } else {
+#pragma unroll
+                for (int m = 0; m < 8; ++m)
+                    if (!shift_voxel_kept(sg, c, w0 + m)) {
+                        const uint32_t keep = (m & 1) ? 0x0000FFFFu : 0xFFFF0000u;
+                        val[m >> 1] = (val[m >> 1] & keep) | (f & ~keep);
+                    }
+            }
+        }
+    }
+    if (NT) __builtin_nontemporal_store(val, dst + i);
+    else dst[i] = val;
+}
+
+hipError_t launch_shift_lines(const ShiftGeom& sg, const void* src, void* dst, uint64_t nvox, int bytes_per_voxel,
+                              uint32_t fill, bool nontemporal, hipStream_t s) {
+    if (nvox == 0) return hipSuccess;
+    if (src == dst || nvox % kLineVoxels) return hipErrorInvalidValue;
+    const uint64_t nvec = nvox * (uint64_t)bytes_per_voxel / 16;
+    const uint64_t blocks = (nvec + 255) / 256;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 gr((unsigned)blocks), bl(256);
+    const u32x4* a = static_cast<const u32x4*>(src);
+    u32x4* b = static_cast<u32x4*>(dst);
+#define SEMTSDF_SHIFT_LAUNCH(BPV)                                                                       \
+    if (nontemporal) hipLaunchKernelGGL((k_shift_lines<BPV, true>), gr, bl, 0, s, sg, a, b, nvec, fill); \
+    else hipLaunchKernelGGL((k_shift_lines<BPV, false>), gr, bl, 0, s, sg, a, b, nvec, fill)
+    switch (bytes_per_voxel) {
+        case 2: SEMTSDF_SHIFT_LAUNCH(2); break;
+        case 4: SEMTSDF_SHIFT_LAUNCH(4); break;
+        case 16: SEMTSDF_SHIFT_LAUNCH(16); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef SEMTSDF_SHIFT_LAUNCH
     return hipGetLastError();
 }
 

@@ -203,6 +203,7 @@ SIGNATURES = {
     "semtsdf_set_state": (_I, [_P, C.c_uint32, C.c_int32]),
     "semtsdf_get_stream": (_P, [_P]),
     "semtsdf_reset": (_I, [_P, _P]),
+    "semtsdf_shift": (_I, [_P, _P, _P]),
     "semtsdf_integrate": (_I, [_P, _P, _P, _P, _P, _P]),
     "semtsdf_integrate_dev": (_I, [_P, _P, _P, _P, _P, _P]),
     "semtsdf_integrate_dev_async": (_I, [_P, _P, _P, _P, _P, _P, _P]),

@@ -157,6 +157,33 @@ class TSDF:
         self.last_extrinsic = np.array(extrinsic, dtype=np.float64)
         return st
 
+    def follow(self, extrinsic, focus_depth=None, trigger_bricks: int = 2, on_evict=None, sdf_max: float = 0.2,
+               min_weight: int = 1):
+        """Recentre the volume on what the camera at `extrinsic` (W2C, as parse_frame takes it)
+        looks at, `focus_depth` metres ahead (by default the mean depth of the first frame):
+        semtsdf.follow.plan_shift decides, Volume.shift moves the voxels by whole bricks on the
+        device, vol_start / vol_end follow.  Returns the shift (sx, sy, sz) in voxels, or None when
+        none was due (or nothing is placed yet).  on_evict, if given, is called before the shift
+        with the surface points about to leave (semtsdf.follow.evicted_points with sdf_max and
+        min_weight).  Intended use: t.follow(pose); t.parse_frame(..., pose, ...)."""
+        from .follow import evicted_points, plan_shift
+
+        if not self.init or self.vol is None:
+            return None
+        p = self.vol.params
+        E = P.relative_pose(extrinsic, self.init_extrinsic_inv)
+        shift = plan_shift(list(p.vol_start), list(p.vol_end), list(p.voxel), E,
+                           self.mean_depth if focus_depth is None else focus_depth, trigger_bricks)
+        if shift is None:
+            return None
+        if on_evict is not None:
+            on_evict(evicted_points(self.vol, shift, sdf_max, min_weight))
+        self.vol.shift(*shift)
+        p = self.vol.params
+        self.vol_start = np.array(p.vol_start[:], dtype=np.asarray(self.vol_start).dtype)
+        self.vol_end = np.array(p.vol_end[:], dtype=np.asarray(self.vol_end).dtype)
+        return shift
+
     def _vote_frame(self, depth, color, cls, E):
         from .volume import DeviceBuffer
 

@@ -112,6 +112,14 @@ class Volume:
     def reset(self):
         L.check(L.load().semtsdf_reset(self._h, None))
 
+    def shift(self, sx: int, sy: int, sz: int, stream=None):
+        """Move the volume by whole bricks (semtsdf_shift): voxel i then holds what voxel i + s
+        held, what slides in is the reset state, and vol_start / vol_end move with it.  Each
+        component is a multiple of 8 voxels.  `params` is refreshed from the handle."""
+        s = np.array([int(sx), int(sy), int(sz)], np.int32)
+        L.check(L.load().semtsdf_shift(self._h, L.ptr(s), stream))
+        self.params = self.get_params()
+
     def get_params(self) -> L.Params:
         p = L.Params()
         L.check(L.load().semtsdf_get_params(self._h, C.byref(p)))
