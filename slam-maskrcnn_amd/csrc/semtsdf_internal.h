@@ -316,7 +316,7 @@ struct FrameMapsArgs {
 
 constexpr int kIcpWords = 32;  // SEMTSDF_ICP_WORDS
 
-// The point-to-plane system of one ICP iteration (k_icp_system, include/semtsdf.h).
+// The point-to-plane system of one ICP iteration (k_track_system<false>, include/semtsdf.h).
 struct IcpArgs {
     const float* vertex;    // frame maps
     const float* normal;
@@ -366,7 +366,7 @@ struct IntensityArgs {
 
 constexpr int kRgbdWords = 64;  // SEMTSDF_RGBD_WORDS: the geometric system's 32 words, then the photometric 32
 
-// The RGB-D system of one iteration (k_rgbd_system): IcpArgs' inputs on the grid of pyramid level l
+// The RGB-D system of one iteration (k_track_system<true>): IcpArgs' inputs on the grid of pyramid level l
 // (fwidth x fheight = (W >> l) x (H >> l)) and both intensity pyramids' level l on that grid.
 struct RgbdArgs {
     IcpArgs icp;            // words: [kRgbdWords], zeroed before the launch

@@ -26,6 +26,7 @@
 #include <limits.h>
 #include <stddef.h>
 #include <stdlib.h>
+#include <type_traits>
 #include "semtsdf_internal.h"
 #include "semtsdf_libm.h"
 #include "semtsdf_shift.h"
@@ -3603,9 +3604,9 @@ hipError_t launch_model_maps(const MapsArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------
-// camera tracking (include/semtsdf.h, "camera tracking"): the frame maps of a depth image and
-// the point-to-plane system of one ICP iteration.  Two flat per-pixel kernels, no march; the
-// volume is not read.  No reference counterpart.
+// camera tracking (include/semtsdf.h, "camera tracking"): the frame maps of a depth image, a flat
+// per-pixel kernel; the system of one iteration is k_track_system below.  No march; the volume is
+// not read.  No reference counterpart.
 // ------------------------------------------------------------------------------------
 __device__ __forceinline__ void cross3(const float a[3], const float b[3], float out[3]) {
     out[0] = a[1] * b[2] - a[2] * b[1];
@@ -3830,122 +3831,8 @@ hipError_t launch_depth_halve(const DepthHalveArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// RN(a * b * 2^32) as an integer: the double product of two f32 values is exact, and so is the
-// scaling; |a b| < 2^10 by the range gate, so the result is far inside int64.
-__device__ __forceinline__ long long icp_fix(float a, float b) {
-    return __double2ll_rn((double)a * (double)b * 4294967296.0);
-}
-
-constexpr int kIcpSums = 28;  // words 0..27: J^T J (21), J^T r (6), sum r^2; 28..31 are the class counts
-
-// One thread per visited pixel (16 x 16 tiles of the strided pixel grid).  An inlier's 28 terms are
-// summed over the wave by a butterfly of shuffles (both halves of each word), the four class
-// counts come from ballots; the waves of a workgroup meet in LDS and the workgroup adds each
-// nonzero word to the output with one 64-bit integer atomic.  Integer sums: no order dependence.
-__global__ __launch_bounds__(256) void k_icp_system(IcpArgs a) {
-    __shared__ long long red[4][kIcpWords];
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long xl = ((long long)blockIdx.x * 16 + (tid & 15)) * a.stride;
-    const long long yl = ((long long)blockIdx.y * 16 + (tid >> 4)) * a.stride;
-    int cls = -1;  // 0 inlier, 1 far, 2 angle, 3 none; -1: not visited
-    float J[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, r = 0.0f;
-    if (xl < a.fwidth && yl < a.fheight) {  // the frame's grid; the model's (width, height) bounds the projection
-        const size_t px = (size_t)yl * a.fwidth + (size_t)xl;
-        if ((a.flags[px] & 3u) == 3u) {
-            cls = 3;
-            const float V0 = a.vertex[px * 3 + 0], V1 = a.vertex[px * 3 + 1], V2 = a.vertex[px * 3 + 2];
-            float Pw[3];
-            Pw[0] = dot3(a.Rt[0], a.Rt[1], a.Rt[2], V0, V1, V2) + a.o[0];
-            Pw[1] = dot3(a.Rt[3], a.Rt[4], a.Rt[5], V0, V1, V2) + a.o[1];
-            Pw[2] = dot3(a.Rt[6], a.Rt[7], a.Rt[8], V0, V1, V2) + a.o[2];
-            const float qx = dot3(a.Eref[0], a.Eref[1], a.Eref[2], Pw[0], Pw[1], Pw[2]) + a.Eref[3];
-            const float qy = dot3(a.Eref[4], a.Eref[5], a.Eref[6], Pw[0], Pw[1], Pw[2]) + a.Eref[7];
-            const float qz = dot3(a.Eref[8], a.Eref[9], a.Eref[10], Pw[0], Pw[1], Pw[2]) + a.Eref[11];
-            const float sx = dot3(a.K[0], a.K[1], a.K[2], qx, qy, qz);
-            const float sy = dot3(a.K[3], a.K[4], a.K[5], qx, qy, qz);
-            const float sz = dot3(a.K[6], a.K[7], a.K[8], qx, qy, qz);
-            const float u = floorf(sx / sz + 0.5f), v = floorf(sy / sz + 0.5f);
-            if (!(qz <= 0.0f) && u >= 0.0f && u < (float)a.width && v >= 0.0f && v < (float)a.height) {
-                const size_t mp = (size_t)(int)v * a.width + (size_t)(int)u;
-                if ((a.m_flags[mp] & 3u) == 3u) {
-                    float Nm[3], d[3];
-                    for (int k = 0; k < 3; ++k) {
-                        Nm[k] = a.m_normal[mp * 3 + k];
-                        d[k] = a.m_point[mp * 3 + k] - Pw[k];
-                    }
-                    if (dot3(d[0], d[1], d[2], d[0], d[1], d[2]) > a.dmax2) {
-                        cls = 1;
-                    } else {
-                        const float n0 = a.normal[px * 3 + 0], n1 = a.normal[px * 3 + 1], n2 = a.normal[px * 3 + 2];
-                        const float w0 = dot3(a.Rt[0], a.Rt[1], a.Rt[2], n0, n1, n2);
-                        const float w1 = dot3(a.Rt[3], a.Rt[4], a.Rt[5], n0, n1, n2);
-                        const float w2 = dot3(a.Rt[6], a.Rt[7], a.Rt[8], n0, n1, n2);
-                        if (dot3(Nm[0], Nm[1], Nm[2], w0, w1, w2) < a.cos_min) {
-                            cls = 2;
-                        } else {
-                            r = dot3(Nm[0], Nm[1], Nm[2], d[0], d[1], d[2]);
-                            cross3(Pw, Nm, J);
-                            J[3] = Nm[0];
-                            J[4] = Nm[1];
-                            J[5] = Nm[2];
-                            bool in = true;
-                            for (int k = 0; k < 6; ++k) in = in && fabsf(J[k]) < 32.0f;
-                            if (in) cls = 0;
-                        }
-                    }
-                }
-            }
-        }
-    }
-    // the ballots are taken by the whole wave, before lane 0 alone stores their counts
-    const unsigned long long inl = __ballot(cls == 0), far = __ballot(cls == 1), ang = __ballot(cls == 2),
-                             non = __ballot(cls == 3);
-    if (lane == 0) {
-        red[wave][28] = (long long)__popcll(inl);
-        red[wave][29] = (long long)__popcll(far);
-        red[wave][30] = (long long)__popcll(ang);
-        red[wave][31] = (long long)__popcll(non);
-    }
-    if (inl) {  // wave-uniform
-        long long acc[kIcpSums];
-        if (cls != 0) {
-            for (int k = 0; k < 6; ++k) J[k] = 0.0f;
-            r = 0.0f;
-        }
-        int w = 0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-#pragma unroll
-            for (int j = i; j < 6; ++j) acc[w++] = icp_fix(J[i], J[j]);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) acc[21 + i] = icp_fix(J[i], r);
-        acc[27] = icp_fix(r, r);
-#pragma unroll
-        for (int k = 0; k < kIcpSums; ++k) {
-            long long s = acc[k];
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-            if (lane == 0) red[wave][k] = s;
-        }
-    } else if (lane < kIcpSums) {
-        red[wave][lane] = 0;
-    }
-    __syncthreads();
-    if (tid < kIcpWords) {
-        const long long s = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-        if (s) atomicAdd(reinterpret_cast<unsigned long long*>(a.words) + tid, (unsigned long long)s);
-    }
-}
-
-hipError_t launch_icp_system(const IcpArgs& a, hipStream_t s) {
-    const int nx = (a.fwidth - 1) / a.stride + 1, ny = (a.fheight - 1) / a.stride + 1;  // visited pixels
-    const dim3 grid((nx + 15) / 16, (ny + 15) / 16);
-    hipLaunchKernelGGL(k_icp_system, grid, dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------
-// RGB-D tracking (include/semtsdf.h, "RGB-D tracking"): the intensity pyramid of a colour image and
-// the system of one iteration with a photometric term beside the point-to-plane one.
+// RGB-D tracking (include/semtsdf.h, "RGB-D tracking"): the intensity pyramid of a colour image.
 // ------------------------------------------------------------------------------------
 constexpr unsigned kIntensityOk = 0x80000000u;  // bit 31 of a staged sum: valid (S_3 <= 16320 * 64 < 2^20)
 
@@ -4019,26 +3906,159 @@ hipError_t launch_intensity_pyramid(const IntensityArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// RN(a * b * 2^20): the photometric words' scale; |a b| < 2^22 by their range gate.
-__device__ __forceinline__ long long rgbd_fix(float a, float b) {
-    return __double2ll_rn((double)a * (double)b * 1048576.0);
+// ------------------------------------------------------------------------------------
+// The system of one tracking iteration (include/semtsdf.h, "camera tracking" and "RGB-D tracking"):
+// one row rule and one accumulation, used by both instantiations of one kernel.
+// ------------------------------------------------------------------------------------
+constexpr int kIcpSums = 28;  // words 0..27 of a system: J^T J (21), J^T r (6), sum r^2; 28..31 are its class counts
+
+// Steps 1-2 of both rules: Pw of frame pixel px, q = E_ref Pw and the model pixel mp that q rounds to.
+// False where q lies behind the reference camera or rounds off the model's grid (mp is not set then).
+__device__ __forceinline__ bool track_project(const IcpArgs& a, size_t px, float Pw[3], float q[3], size_t& mp) {
+    const float V0 = a.vertex[px * 3 + 0], V1 = a.vertex[px * 3 + 1], V2 = a.vertex[px * 3 + 2];
+    Pw[0] = dot3(a.Rt[0], a.Rt[1], a.Rt[2], V0, V1, V2) + a.o[0];
+    Pw[1] = dot3(a.Rt[3], a.Rt[4], a.Rt[5], V0, V1, V2) + a.o[1];
+    Pw[2] = dot3(a.Rt[6], a.Rt[7], a.Rt[8], V0, V1, V2) + a.o[2];
+    q[0] = dot3(a.Eref[0], a.Eref[1], a.Eref[2], Pw[0], Pw[1], Pw[2]) + a.Eref[3];
+    q[1] = dot3(a.Eref[4], a.Eref[5], a.Eref[6], Pw[0], Pw[1], Pw[2]) + a.Eref[7];
+    q[2] = dot3(a.Eref[8], a.Eref[9], a.Eref[10], Pw[0], Pw[1], Pw[2]) + a.Eref[11];
+    const float sx = dot3(a.K[0], a.K[1], a.K[2], q[0], q[1], q[2]);
+    const float sy = dot3(a.K[3], a.K[4], a.K[5], q[0], q[1], q[2]);
+    const float sz = dot3(a.K[6], a.K[7], a.K[8], q[0], q[1], q[2]);
+    const float u = floorf(sx / sz + 0.5f), v = floorf(sy / sz + 0.5f);
+    const bool on = !(q[2] <= 0.0f) && u >= 0.0f && u < (float)a.width && v >= 0.0f && v < (float)a.height;
+    if (on) mp = (size_t)(int)v * a.width + (size_t)(int)u;
+    return on;
 }
 
-constexpr int kRgbdGrid = 256;  // persistent workgroups at most: one per CU
+// Step 3 of both rules: d = Pm - Pw at model pixel mp, and whether it fails the distance gate.
+__device__ __forceinline__ bool track_offset(const IcpArgs& a, size_t mp, const float Pw[3], float d[3]) {
+    for (int k = 0; k < 3; ++k) d[k] = a.m_point[mp * 3 + k] - Pw[k];
+    return dot3(d[0], d[1], d[2], d[0], d[1], d[2]) > a.dmax2;
+}
 
-// At most kRgbdGrid persistent workgroups walk the 16 x 16 tiles of the strided pixel grid with a grid
-// stride, one thread per visited pixel of a tile.  Every lane keeps its 2 x 28 sums in int64 registers
-// across all its tiles and the eight class counts come from ballots; at the end one butterfly per wave,
-// one meeting in LDS and one 64-bit integer atomic per nonzero word per workgroup.  The geometric half
-// is k_icp_system's rule step by step, so words 0..31 are that kernel's.
-__global__ __launch_bounds__(256) void k_rgbd_system(RgbdArgs g, int tiles_x, int ntiles) {
-    __shared__ long long red[4][kRgbdWords];
+// Steps 3-5 of the point-to-plane rule at a model pixel with a hit and a normal, from track_offset's d
+// and far: the class (0 inlier, 1 far, 2 angle, 3 none) and, for an inlier, its row J and residual r.
+__device__ __forceinline__ int icp_row(const IcpArgs& a, size_t px, size_t mp, const float Pw[3], const float d[3],
+                                       bool far, float J[6], float& r) {
+    if (far) return 1;
+    float Nm[3];
+    for (int k = 0; k < 3; ++k) Nm[k] = a.m_normal[mp * 3 + k];
+    const float n0 = a.normal[px * 3 + 0], n1 = a.normal[px * 3 + 1], n2 = a.normal[px * 3 + 2];
+    const float w0 = dot3(a.Rt[0], a.Rt[1], a.Rt[2], n0, n1, n2);
+    const float w1 = dot3(a.Rt[3], a.Rt[4], a.Rt[5], n0, n1, n2);
+    const float w2 = dot3(a.Rt[6], a.Rt[7], a.Rt[8], n0, n1, n2);
+    if (dot3(Nm[0], Nm[1], Nm[2], w0, w1, w2) < a.cos_min) return 2;
+    r = dot3(Nm[0], Nm[1], Nm[2], d[0], d[1], d[2]);
+    cross3(Pw, Nm, J);
+    J[3] = Nm[0];
+    J[4] = Nm[1];
+    J[5] = Nm[2];
+    bool in = true;
+    for (int k = 0; k < 6; ++k) in = in && fabsf(J[k]) < 32.0f;
+    return in ? 0 : 3;
+}
+
+// Steps 3-7 of the photometric rule at a model pixel with a hit, from track_offset's far: the class
+// (0 inlier, 1 far, 2 outlier, 3 none) and, for an inlier, its row Jp and residual rp.
+__device__ __forceinline__ int photo_row(const RgbdArgs& g, size_t px, const float Pw[3], const float q[3], bool far,
+                                         float Jp[6], float& rp) {
     const IcpArgs& a = g.icp;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long acc[2 * kIcpSums];
+    if (far) return 1;
+    const float iz = 1.0f / q[2];
+    const float ul = fmaf(g.fxl, q[0] * iz, g.cxl), vl = fmaf(g.fyl, q[1] * iz, g.cyl);
+    const float fx0 = floorf(ul), fy0 = floorf(vl);
+    if (!(fx0 >= 0.0f && fx0 + 1.0f < (float)a.fwidth && fy0 >= 0.0f && fy0 + 1.0f < (float)a.fheight)) return 3;
+    const size_t lp = (size_t)(int)fy0 * a.fwidth + (size_t)(int)fx0;
+    // the four taps lie on the grid, so their validity, their sums and the frame's sum are all loaded in
+    // one round trip, before the validity is looked at
+    const size_t lq = lp + a.fwidth;
+    const unsigned ok00 = g.m_ok[lp], ok10 = g.m_ok[lp + 1], ok01 = g.m_ok[lq], ok11 = g.m_ok[lq + 1];
+    const unsigned S00 = g.m_S[lp], S10 = g.m_S[lp + 1], S01 = g.m_S[lq], S11 = g.m_S[lq + 1], Sf = g.f_S[px];
+    if (!((ok00 != 0u) & (ok10 != 0u) & (ok01 != 0u) & (ok11 != 0u))) return 3;
+    const float ax = ul - fx0, ay = vl - fy0;
+    const float m00 = (float)S00 * g.iscale, m10 = (float)S10 * g.iscale;
+    const float m01 = (float)S01 * g.iscale;
+    const float m11 = (float)S11 * g.iscale;
+    const float dx0 = m10 - m00, dx1 = m11 - m01, dy0 = m01 - m00;
+    const float top = fmaf(ax, dx0, m00), bot = fmaf(ax, dx1, m01);
+    const float Im = fmaf(ay, bot - top, top);
+    const float gx = fmaf(ay, dx1 - dx0, dx0);
+    const float gy = fmaf(ax, (m11 - m10) - dy0, dy0);
+    rp = (float)Sf * g.iscale - Im;
+    if (fabsf(rp) > g.r_max) return 2;
+    const float a0 = (gx * g.fxl) * iz, a1 = (gy * g.fyl) * iz;
+    const float a2 = -((a0 * q[0] + a1 * q[1]) * iz);
+    float aw[3];
+    aw[0] = dot3(a.Eref[0], a.Eref[4], a.Eref[8], a0, a1, a2);
+    aw[1] = dot3(a.Eref[1], a.Eref[5], a.Eref[9], a0, a1, a2);
+    aw[2] = dot3(a.Eref[2], a.Eref[6], a.Eref[10], a0, a1, a2);
+    cross3(Pw, aw, Jp);
+    Jp[3] = aw[0];
+    Jp[4] = aw[1];
+    Jp[5] = aw[2];
+    bool in = true;
+    for (int k = 0; k < 6; ++k) in = in && fabsf(Jp[k]) < 2048.0f;
+    return in ? 0 : 3;
+}
+
+// Adds the four class ballots of the wave into its counters and returns the inliers' ballot; called by
+// the whole wave (cls -1: a lane that visits no pixel).
+__device__ __forceinline__ unsigned long long track_count(unsigned cnt[4], int cls) {
+    const unsigned long long inl = __ballot(cls == 0);
+    cnt[0] += __popcll(inl);
+    cnt[1] += __popcll(__ballot(cls == 1));
+    cnt[2] += __popcll(__ballot(cls == 2));
+    cnt[3] += __popcll(__ballot(cls == 3));
+    return inl;
+}
+
+// Adds the 28 terms of a row to acc, each RN(x y scale) as an integer: the double product of two f32
+// values is exact and so is the scaling by a power of two (2^32 with |x y| < 2^10, 2^20 with
+// |x y| < 2^22, by the range gates: far inside int64).  A lane that is no inlier adds zeros.
+__device__ __forceinline__ void track_accumulate(long long acc[kIcpSums], bool in, const float J[6], float r,
+                                                 double scale) {
+    float t[7];  // J, then r
+    for (int k = 0; k < 6; ++k) t[k] = J[k];
+    t[6] = r;
+    if (!in) {
+        for (int k = 0; k < 7; ++k) t[k] = 0.0f;
+    }
+    int w = 0;
 #pragma unroll
-    for (int k = 0; k < 2 * kIcpSums; ++k) acc[k] = 0;
-    unsigned cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // wave-uniform; at most 2^19 pixels are visited
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) acc[w++] += __double2ll_rn((double)t[i] * (double)t[j] * scale);
+#pragma unroll
+    for (int i = 0; i < 7; ++i) acc[21 + i] += __double2ll_rn((double)t[i] * (double)t[6] * scale);
+}
+
+__host__ __device__ __forceinline__ const IcpArgs& icp_args(const IcpArgs& a) { return a; }
+__host__ __device__ __forceinline__ const IcpArgs& icp_args(const RgbdArgs& g) { return g.icp; }
+
+// Persistent workgroups at most: one per CU.  The tests hold both regimes of the tile loop for both
+// instantiations: the ragged 75 x 53 field has 20 tiles at most, so the grid is ntiles and every
+// workgroup makes one trip; 640 x 480 at stride 1 has 1200 tiles, four full trips of 256 and a fifth of
+// 176, and reaches all four classes of both rows.
+constexpr int kTrackGrid = 256;
+
+// At most kTrackGrid persistent workgroups walk the 16 x 16 tiles of the strided pixel grid with a grid
+// stride, one thread per visited pixel of a tile.  Every lane keeps its 28 sums per system in int64
+// registers across all its tiles and the class counts come from ballots; at the end one butterfly per
+// wave, one meeting in LDS and one 64-bit integer atomic per nonzero word per workgroup.  Integer
+// sums: no order dependence.  PHOTO false: words 0..31, the point-to-plane system of an IcpArgs;
+// true: the photometric system of a RgbdArgs beside it in words 32..63.
+template <bool PHOTO>
+__global__ __launch_bounds__(256) void k_track_system(std::conditional_t<PHOTO, RgbdArgs, IcpArgs> g, int tiles_x,
+                                                      int ntiles) {
+    constexpr int NS = PHOTO ? 2 : 1;  // systems formed
+    __shared__ long long red[4][NS * kIcpWords];
+    const IcpArgs& a = icp_args(g);
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    long long acc[NS * kIcpSums];
+#pragma unroll
+    for (int k = 0; k < NS * kIcpSums; ++k) acc[k] = 0;
+    unsigned cnt[NS * 4] = {};  // wave-uniform; at most 2^19 pixels are visited
     for (int tile = (int)blockIdx.x; tile < ntiles; tile += (int)gridDim.x) {
         const int by = tile / tiles_x, bx = tile - by * tiles_x;
         const long long xl = ((long long)bx * 16 + (tid & 15)) * a.stride;
@@ -4046,166 +4066,64 @@ __global__ __launch_bounds__(256) void k_rgbd_system(RgbdArgs g, int tiles_x, in
         int cls = -1, pcls = -1;  // 0 inlier, 1 far, 2 angle / outlier, 3 none; -1: not visited
         float J[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, r = 0.0f;
         float Jp[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, rp = 0.0f;
-        if (xl < a.fwidth && yl < a.fheight) {
+        if (xl < a.fwidth && yl < a.fheight) {  // the frame's grid; the model's (width, height) bounds the projection
             const size_t px = (size_t)yl * a.fwidth + (size_t)xl;
             const unsigned fl = a.flags[px];
             if ((fl & 3u) == 3u) cls = 3;
-            if ((fl & 1u) && g.f_ok[px]) pcls = 3;
-            if (cls == 3 || pcls == 3) {
-                const float V0 = a.vertex[px * 3 + 0], V1 = a.vertex[px * 3 + 1], V2 = a.vertex[px * 3 + 2];
-                float Pw[3];
-                Pw[0] = dot3(a.Rt[0], a.Rt[1], a.Rt[2], V0, V1, V2) + a.o[0];
-                Pw[1] = dot3(a.Rt[3], a.Rt[4], a.Rt[5], V0, V1, V2) + a.o[1];
-                Pw[2] = dot3(a.Rt[6], a.Rt[7], a.Rt[8], V0, V1, V2) + a.o[2];
-                const float qx = dot3(a.Eref[0], a.Eref[1], a.Eref[2], Pw[0], Pw[1], Pw[2]) + a.Eref[3];
-                const float qy = dot3(a.Eref[4], a.Eref[5], a.Eref[6], Pw[0], Pw[1], Pw[2]) + a.Eref[7];
-                const float qz = dot3(a.Eref[8], a.Eref[9], a.Eref[10], Pw[0], Pw[1], Pw[2]) + a.Eref[11];
-                const float sx = dot3(a.K[0], a.K[1], a.K[2], qx, qy, qz);
-                const float sy = dot3(a.K[3], a.K[4], a.K[5], qx, qy, qz);
-                const float sz = dot3(a.K[6], a.K[7], a.K[8], qx, qy, qz);
-                const float u = floorf(sx / sz + 0.5f), v = floorf(sy / sz + 0.5f);
-                if (!(qz <= 0.0f) && u >= 0.0f && u < (float)a.width && v >= 0.0f && v < (float)a.height) {
-                    const size_t mp = (size_t)(int)v * a.width + (size_t)(int)u;
-                    const unsigned mf = a.m_flags[mp];
-                    if (mf & 1u) {
-                        float d[3];
-                        for (int k = 0; k < 3; ++k) d[k] = a.m_point[mp * 3 + k] - Pw[k];
-                        const bool far = dot3(d[0], d[1], d[2], d[0], d[1], d[2]) > a.dmax2;
-                        if (cls == 3 && (mf & 3u) == 3u) {  // the point-to-plane row: k_icp_system's steps 3..5
-                            if (far) {
-                                cls = 1;
-                            } else {
-                                float Nm[3];
-                                for (int k = 0; k < 3; ++k) Nm[k] = a.m_normal[mp * 3 + k];
-                                const float n0 = a.normal[px * 3 + 0], n1 = a.normal[px * 3 + 1], n2 = a.normal[px * 3 + 2];
-                                const float w0 = dot3(a.Rt[0], a.Rt[1], a.Rt[2], n0, n1, n2);
-                                const float w1 = dot3(a.Rt[3], a.Rt[4], a.Rt[5], n0, n1, n2);
-                                const float w2 = dot3(a.Rt[6], a.Rt[7], a.Rt[8], n0, n1, n2);
-                                if (dot3(Nm[0], Nm[1], Nm[2], w0, w1, w2) < a.cos_min) {
-                                    cls = 2;
-                                } else {
-                                    r = dot3(Nm[0], Nm[1], Nm[2], d[0], d[1], d[2]);
-                                    cross3(Pw, Nm, J);
-                                    J[3] = Nm[0];
-                                    J[4] = Nm[1];
-                                    J[5] = Nm[2];
-                                    bool in = true;
-                                    for (int k = 0; k < 6; ++k) in = in && fabsf(J[k]) < 32.0f;
-                                    if (in) cls = 0;
-                                }
-                            }
-                        }
-                        if (pcls == 3) {  // the photometric row: steps 3..7
-                            if (far) {
-                                pcls = 1;
-                            } else {
-                                const float iz = 1.0f / qz;
-                                const float ul = fmaf(g.fxl, qx * iz, g.cxl), vl = fmaf(g.fyl, qy * iz, g.cyl);
-                                const float fx0 = floorf(ul), fy0 = floorf(vl);
-                                if (fx0 >= 0.0f && fx0 + 1.0f < (float)a.fwidth && fy0 >= 0.0f &&
-                                    fy0 + 1.0f < (float)a.fheight) {
-                                    const size_t lp = (size_t)(int)fy0 * a.fwidth + (size_t)(int)fx0;
-                                    if (g.m_ok[lp] && g.m_ok[lp + 1] && g.m_ok[lp + a.fwidth] && g.m_ok[lp + a.fwidth + 1]) {
-                                        const float ax = ul - fx0, ay = vl - fy0;
-                                        const float m00 = (float)g.m_S[lp] * g.iscale, m10 = (float)g.m_S[lp + 1] * g.iscale;
-                                        const float m01 = (float)g.m_S[lp + a.fwidth] * g.iscale;
-                                        const float m11 = (float)g.m_S[lp + a.fwidth + 1] * g.iscale;
-                                        const float dx0 = m10 - m00, dx1 = m11 - m01, dy0 = m01 - m00;
-                                        const float top = fmaf(ax, dx0, m00), bot = fmaf(ax, dx1, m01);
-                                        const float Im = fmaf(ay, bot - top, top);
-                                        const float gx = fmaf(ay, dx1 - dx0, dx0);
-                                        const float gy = fmaf(ax, (m11 - m10) - dy0, dy0);
-                                        const float res = (float)g.f_S[px] * g.iscale - Im;
-                                        if (fabsf(res) > g.r_max) {
-                                            pcls = 2;
-                                        } else {
-                                            const float a0 = (gx * g.fxl) * iz, a1 = (gy * g.fyl) * iz;
-                                            const float a2 = -((a0 * qx + a1 * qy) * iz);
-                                            float aw[3];
-                                            aw[0] = dot3(a.Eref[0], a.Eref[4], a.Eref[8], a0, a1, a2);
-                                            aw[1] = dot3(a.Eref[1], a.Eref[5], a.Eref[9], a0, a1, a2);
-                                            aw[2] = dot3(a.Eref[2], a.Eref[6], a.Eref[10], a0, a1, a2);
-                                            cross3(Pw, aw, Jp);
-                                            Jp[3] = aw[0];
-                                            Jp[4] = aw[1];
-                                            Jp[5] = aw[2];
-                                            bool in = true;
-                                            for (int k = 0; k < 6; ++k) in = in && fabsf(Jp[k]) < 2048.0f;
-                                            if (in) {
-                                                pcls = 0;
-                                                rp = res;
-                                            }
-                                        }
-                                    }
-                                }
-                            }
-                        }
+            if constexpr (PHOTO) {
+                if (((fl & 1u) != 0u) & (g.f_ok[px] != 0)) pcls = 3;  // both bytes in one round trip
+            }
+            float Pw[3], q[3];
+            size_t mp;
+            if ((cls == 3 || pcls == 3) && track_project(a, px, Pw, q, mp)) {
+                // the model point is read where a row can use it: a hit for the photometric row, a hit
+                // with a normal for the point-to-plane row, which stays none without the normal
+                const unsigned mf = a.m_flags[mp];
+                if (PHOTO ? (mf & 1u) != 0u : (mf & 3u) == 3u) {
+                    float d[3];
+                    const bool far = track_offset(a, mp, Pw, d);
+                    if (cls == 3 && (mf & 3u) == 3u) cls = icp_row(a, px, mp, Pw, d, far, J, r);
+                    if constexpr (PHOTO) {
+                        if (pcls == 3) pcls = photo_row(g, px, Pw, q, far, Jp, rp);
                     }
                 }
             }
         }
-        // the ballots are taken by the whole wave
-        const unsigned long long inl = __ballot(cls == 0), pinl = __ballot(pcls == 0);
-        cnt[0] += __popcll(inl);
-        cnt[1] += __popcll(__ballot(cls == 1));
-        cnt[2] += __popcll(__ballot(cls == 2));
-        cnt[3] += __popcll(__ballot(cls == 3));
-        cnt[4] += __popcll(pinl);
-        cnt[5] += __popcll(__ballot(pcls == 1));
-        cnt[6] += __popcll(__ballot(pcls == 2));
-        cnt[7] += __popcll(__ballot(pcls == 3));
-        if (inl) {  // wave-uniform; a lane that is no inlier adds zeros
-            if (cls != 0) {
-                for (int k = 0; k < 6; ++k) J[k] = 0.0f;
-                r = 0.0f;
-            }
-            int w = 0;
-#pragma unroll
-            for (int i = 0; i < 6; ++i)
-#pragma unroll
-                for (int j = i; j < 6; ++j) acc[w++] += icp_fix(J[i], J[j]);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) acc[21 + i] += icp_fix(J[i], r);
-            acc[27] += icp_fix(r, r);
-        }
-        if (pinl) {
-            if (pcls != 0) {
-                for (int k = 0; k < 6; ++k) Jp[k] = 0.0f;
-                rp = 0.0f;
-            }
-            int w = kIcpSums;
-#pragma unroll
-            for (int i = 0; i < 6; ++i)
-#pragma unroll
-                for (int j = i; j < 6; ++j) acc[w++] += rgbd_fix(Jp[i], Jp[j]);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) acc[kIcpSums + 21 + i] += rgbd_fix(Jp[i], rp);
-            acc[kIcpSums + 27] += rgbd_fix(rp, rp);
+        // the ballots are taken by the whole wave; the sums are skipped where the wave has no inlier
+        if (track_count(cnt, cls)) track_accumulate(acc, cls == 0, J, r, 4294967296.0);
+        if constexpr (PHOTO) {
+            if (track_count(cnt + 4, pcls)) track_accumulate(acc + kIcpSums, pcls == 0, Jp, rp, 1048576.0);
         }
     }
 #pragma unroll
-    for (int k = 0; k < 2 * kIcpSums; ++k) {
+    for (int k = 0; k < NS * kIcpSums; ++k) {
         long long s = acc[k];
         for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
         if (lane == 0) red[wave][(k / kIcpSums) * kIcpWords + (k % kIcpSums)] = s;
     }
     if (lane == 0) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) red[wave][(k / 4) * kIcpWords + kIcpSums + (k % 4)] = (long long)cnt[k];
+        for (int k = 0; k < NS * 4; ++k) red[wave][(k / 4) * kIcpWords + kIcpSums + (k % 4)] = (long long)cnt[k];
     }
     __syncthreads();
-    if (tid < kRgbdWords) {
+    if (tid < NS * kIcpWords) {
         const long long s = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
         if (s) atomicAdd(reinterpret_cast<unsigned long long*>(a.words) + tid, (unsigned long long)s);
     }
 }
 
-hipError_t launch_rgbd_system(const RgbdArgs& a, hipStream_t s) {
-    const int nx = (a.icp.fwidth - 1) / a.icp.stride + 1, ny = (a.icp.fheight - 1) / a.icp.stride + 1;  // visited pixels
+template <bool PHOTO, class Args>
+static hipError_t launch_track_system(const Args& g, hipStream_t s) {
+    const IcpArgs& a = icp_args(g);
+    const int nx = (a.fwidth - 1) / a.stride + 1, ny = (a.fheight - 1) / a.stride + 1;  // visited pixels
     const int tiles_x = (nx + 15) / 16, ntiles = tiles_x * ((ny + 15) / 16);
-    hipLaunchKernelGGL(k_rgbd_system, dim3(ntiles < kRgbdGrid ? ntiles : kRgbdGrid), dim3(256), 0, s, a, tiles_x, ntiles);
+    hipLaunchKernelGGL(k_track_system<PHOTO>, dim3(ntiles < kTrackGrid ? ntiles : kTrackGrid), dim3(256), 0, s, g, tiles_x,
+                       ntiles);
     return hipGetLastError();
 }
+
+hipError_t launch_icp_system(const IcpArgs& a, hipStream_t s) { return launch_track_system<false>(a, s); }
+hipError_t launch_rgbd_system(const RgbdArgs& a, hipStream_t s) { return launch_track_system<true>(a, s); }
 
 // ------------------------------------------------------------------------------------
 // Z-sharded raycast.  The march of march_ray is sequential along the ray

@@ -18,6 +18,7 @@ r - J xi is the residual after the step to first order, and xi solves (J^T J) xi
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 
@@ -26,9 +27,13 @@ import numpy as np
 from . import _lib as L
 
 SCALE = 2.0 ** -32          # one unit of the fixed-point sums
+PHOTO_SCALE = 2.0 ** -20    # one unit of the photometric sums
 SMALL_ANGLE = 1e-2          # |omega| below which exp() uses its series
 STEP_EPS = 1e-5             # |xi| (radians and metres together) below which the loop stops
 COUNT_NAMES = ("inliers", "far", "angle", "none")
+PHOTO_COUNT_NAMES = ("inliers", "far", "outlier", "none")
+PHOTO_WEIGHT = 0.02         # metres per unit of intensity (the sweep that chose it)
+R_MAX = 0.25                # the gate on the intensity residual, intensities in [0, 1)
 
 
 class TrackingLost(RuntimeError):
@@ -41,17 +46,31 @@ class TrackingLost(RuntimeError):
         self.log = log
 
 
-def system_from_words(words):
-    """(A, b, r2, counts) of the 32 int64 words: the symmetric 6 x 6 A = J^T J, b = J^T r and
-    r2 = sum r^2 scaled back by 2^-32 (float64), and the four class counts as a dict of ints."""
+def _unpack(words, scale, names):
+    """(A, b, r2, counts) of one 32-word block: the symmetric 6 x 6 A = J^T J, b = J^T r and
+    r2 = sum r^2 scaled back (float64), and the four class counts as a dict of ints under `names`."""
     w = np.asarray(words, np.int64).reshape(L.ICP_WORDS)
     A = np.zeros((6, 6), np.float64)
     iu = np.triu_indices(6)  # row-major upper triangle: the word order
-    A[iu] = w[:21].astype(np.float64) * SCALE
+    A[iu] = w[:21].astype(np.float64) * scale
     A = A + np.triu(A, 1).T
-    b = w[21:27].astype(np.float64) * SCALE
-    counts = {n: int(w[28 + k]) for k, n in enumerate(COUNT_NAMES)}
-    return A, b, float(w[27]) * SCALE, counts
+    b = w[21:27].astype(np.float64) * scale
+    counts = {n: int(w[28 + k]) for k, n in enumerate(names)}
+    return A, b, float(w[27]) * scale, counts
+
+
+def system_from_words(words):
+    """(A, b, r2, counts) of the 32 int64 words: the point-to-plane system scaled back by 2^-32
+    (metres), counts inliers, far, angle, none."""
+    return _unpack(words, SCALE, COUNT_NAMES)
+
+
+def rgbd_system_from_words(words):
+    """Two (A, b, r2, counts) tuples of the 64 int64 words: the point-to-plane system as
+    system_from_words returns it and the photometric one (scale 2^-20, units of intensity; counts
+    inliers, far, outlier, none)."""
+    w = np.asarray(words, np.int64).reshape(L.RGBD_WORDS)
+    return system_from_words(w[:L.ICP_WORDS]), _unpack(w[L.ICP_WORDS:], PHOTO_SCALE, PHOTO_COUNT_NAMES)
 
 
 def solve_step(A, b):
@@ -102,178 +121,81 @@ def default_min_inliers(width, height, stride):
     return max(6, (((width - 1) // stride + 1) * ((height - 1) // stride + 1)) // 100)
 
 
+# (level, max iterations, dist_max, cos_min), coarse first: the gates open where the smoothed coarse
+# normals can bear it and close again at full resolution
+PYRAMID_SCHEDULE = ((2, 4, 0.3, 0.6), (1, 5, 0.2, 0.7), (0, 10, 0.1, 0.8))
+
+
+def _loop(system, schedule, need_of, E0, eps, w2=None):
+    """The loop of all three trackers.  Each (level, iters, dist_max, cos_min) entry of `schedule` runs at
+    most `iters` iterations from the previous entry's result, needing need_of(level) inliers:
+    system(level, E_cur, dist_max, cos_min) -> words, solve, step, stop below eps.  level None: one
+    untagged entry, whose log entries carry no `level` and whose TrackingLost messages no prefix.
+    w2 None: 32 words; else 64, and the photometric system joins with weight w2 where it has the
+    needed inliers itself."""
+    E = np.asarray(E0, np.float32).reshape(4, 4).copy()
+    log = []
+    for level, iters, dist_max, cos_min in schedule:
+        need = need_of(level)
+        where = "" if level is None else f"level {level}: "
+        for it in range(int(iters)):
+            words = system(level, E, dist_max, cos_min)
+            if w2 is None:
+                A, b, r2, counts = system_from_words(words)
+            else:
+                (A, b, r2, counts), (Ap, bp, rp2, pc) = rgbd_system_from_words(words)
+            n = counts["inliers"]
+            entry = dict(counts, iter=it, rms=math.sqrt(r2 / n) if n else float("nan"), step=float("nan"))
+            if level is not None:
+                entry["level"] = level
+            if w2 is not None:
+                m = pc["inliers"]
+                used = m >= need and w2 > 0.0
+                entry.update(photo_inliers=m, photo_rms=math.sqrt(rp2 / m) if m else float("nan"), photo_used=used)
+                if used:
+                    A, b = A + w2 * Ap, b + w2 * bp
+            log.append(entry)
+            if n < need:
+                raise TrackingLost(f"{where}iteration {it}: {n} inliers, fewer than {need}", E, log)
+            try:
+                xi = solve_step(A, b)
+            except np.linalg.LinAlgError as e:
+                raise TrackingLost(f"{where}iteration {it}: {e}", E, log) from e
+            entry["step"] = float(np.linalg.norm(xi))
+            E = se3_apply(xi, E)
+            if entry["step"] < eps:
+                break
+    return E, log
+
+
+def _levels(schedule, dims, stride, min_inliers):
+    """(schedule with int levels, need_of) of a coarse-to-fine loop: default_min_inliers of a level's
+    grid dims[level] = (width, height) unless min_inliers is given."""
+    def need_of(level):
+        w, h = dims[level]
+        return default_min_inliers(w, h, int(stride)) if min_inliers is None else min_inliers
+
+    return [(int(level), iters, dist_max, cos_min) for level, iters, dist_max, cos_min in schedule], need_of
+
+
 def track_loop(system, E0, iters=10, min_inliers=6, eps=STEP_EPS):
     """The ICP loop over any source of the words: system(E_cur) -> 32 int64 words.  Returns
     (E, log): the f32 extrinsic after at most `iters` steps (fewer when a step's |xi| falls below
     eps) and one dict per iteration with the four counts, rms = sqrt(sum r^2 / inliers) before the
     step and step = |xi|.  Raises TrackingLost (estimate and log kept) when an iteration finds
     fewer than min_inliers inliers, or its system cannot be solved."""
-    E = np.asarray(E0, np.float32).reshape(4, 4).copy()
-    log = []
-    for it in range(int(iters)):
-        A, b, r2, counts = system_from_words(system(E))
-        n = counts["inliers"]
-        entry = dict(counts, iter=it, rms=math.sqrt(r2 / n) if n else float("nan"), step=float("nan"))
-        log.append(entry)
-        if n < min_inliers:
-            raise TrackingLost(f"iteration {it}: {n} inliers, fewer than {min_inliers}", E, log)
-        try:
-            xi = solve_step(A, b)
-        except np.linalg.LinAlgError as e:
-            raise TrackingLost(f"iteration {it}: {e}", E, log) from e
-        entry["step"] = float(np.linalg.norm(xi))
-        E = se3_apply(xi, E)
-        if entry["step"] < eps:
-            break
-    return E, log
-
-
-def track(vol, depth, E_ref, E0, iters=10, dist_max=0.1, cos_min=0.8, stride=1, min_weight=1, min_inliers=None,
-          eps=STEP_EPS):
-    """Tracks the depth image (u16 [H, W]) against the model in `vol`, starting from the extrinsic
-    E0.  The model maps are rendered once at pose_camera(Kinv, E_ref) (min_weight: the maps'
-    validity threshold) and stay on the device, as do the frame maps; each iteration is one
-    launch and a 256-byte read-back.  min_inliers defaults to default_min_inliers.  Returns
-    (E, log) as track_loop does, and raises TrackingLost like it."""
-    from .maps import pose_camera
-    from .volume import DeviceBuffer
-
-    d = np.ascontiguousarray(depth, dtype=np.uint16)
-    n = vol.W * vol.H
-    if d.size != n:
-        raise ValueError(f"depth must be {vol.H}x{vol.W} u16")
-    if min_inliers is None:
-        min_inliers = default_min_inliers(vol.W, vol.H, int(stride))
-    E_ref = L.f32(E_ref, 16)
-    s2w, c = pose_camera(list(vol.params.Kinv), E_ref)
-    stream = C.c_void_p(vol.stream)
-    sizes = {"depth": 2 * n, "vertex": 12 * n, "normal": 12 * n, "flags": n, "m_point": 12 * n, "m_normal": 12 * n,
-             "m_flags": n, "words": 8 * L.ICP_WORDS}
-    bufs = {}
-    try:
-        for k, size in sizes.items():
-            bufs[k] = DeviceBuffer(size)
-        vol.render_maps_dev(s2w, c, int(min_weight), point=bufs["m_point"].ptr, normal=bufs["m_normal"].ptr,
-                            flags=bufs["m_flags"].ptr)
-        bufs["depth"].upload(d, stream)
-        vol.frame_maps_dev(bufs["depth"].ptr, bufs["vertex"].ptr, bufs["normal"].ptr, bufs["flags"].ptr)
-        pointers = [bufs[k].ptr for k in ("vertex", "normal", "flags", "m_point", "m_normal", "m_flags")]
-        words = np.zeros(L.ICP_WORDS, np.int64)
-
-        def system(E):
-            vol.icp_system_dev(pointers, E_ref, E, dist_max, cos_min, stride, bufs["words"].ptr)
-            bufs["words"].download(words, stream)
-            vol.sync()
-            return words
-
-        return track_loop(system, E0, iters, min_inliers, eps)
-    finally:
-        vol.sync()
-        for b in bufs.values():
-            b.free()
-
-
-# (level, max iterations, dist_max, cos_min), coarse first: the gates open where the smoothed coarse
-# normals can bear it and close again at full resolution
-PYRAMID_SCHEDULE = ((2, 4, 0.3, 0.6), (1, 5, 0.2, 0.7), (0, 10, 0.1, 0.8))
+    return _loop(lambda _level, E, _dist_max, _cos_min: system(E), ((None, iters, None, None),),
+                 lambda _level: min_inliers, E0, eps)
 
 
 def pyramid_loop(system, dims, E0, schedule=PYRAMID_SCHEDULE, stride=1, min_inliers=None, eps=STEP_EPS):
     """The coarse-to-fine loop over any source of the words: system(level, E_cur, dist_max,
     cos_min) -> 32 int64 words, `dims[level]` = (width, height) of that level's frame grid.  Each
-    schedule entry runs track_loop from the previous entry's result, with default_min_inliers of
-    its level's grid unless min_inliers is given.  Returns (E, log); every log entry carries its
-    `level`.  TrackingLost carries the estimate reached and the log of all levels so far."""
-    E = np.asarray(E0, np.float32).reshape(4, 4).copy()
-    log = []
-    for level, iters, dist_max, cos_min in schedule:
-        level = int(level)
-        w, h = dims[level]
-        need = default_min_inliers(w, h, int(stride)) if min_inliers is None else min_inliers
-
-        def tag(entries):
-            return [dict(e, level=level) for e in entries]
-
-        try:
-            E, part = track_loop(lambda Ec: system(level, Ec, dist_max, cos_min), E, iters, need, eps)
-        except TrackingLost as e:
-            raise TrackingLost(f"level {level}: {e}", e.E, log + tag(e.log)) from e
-        log += tag(part)
-    return E, log
-
-
-def track_pyramid(vol, depth, E_ref, E0, schedule=PYRAMID_SCHEDULE, radius=3, sigma_r=0.05, band=None, stride=1,
-                  min_weight=1, min_inliers=None, eps=STEP_EPS):
-    """track() coarse to fine on the depth pyramid (Volume.frame_pyramid_dev: the edge-preserving
-    filter of `radius`, `sigma_r`, halvings within `band`).  The model maps are rendered once at full
-    resolution and the pyramid is built once, as many levels as the schedule's coarsest entry needs;
-    everything stays on the device and each iteration is one launch (icp_system_level_dev) and a
-    256-byte read-back.  Returns (E, log) as pyramid_loop does, and raises TrackingLost like it."""
-    from .maps import pose_camera
-    from .volume import DeviceBuffer
-
-    d = np.ascontiguousarray(depth, dtype=np.uint16)
-    n = vol.W * vol.H
-    if d.size != n:
-        raise ValueError(f"depth must be {vol.H}x{vol.W} u16")
-    schedule = tuple(tuple(s) for s in schedule)
-    if not schedule or min(int(s[0]) for s in schedule) < 0:
-        raise ValueError("schedule: (level, iterations, dist_max, cos_min) entries with level >= 0")
-    nlevels = max(int(s[0]) for s in schedule) + 1
-    geo = vol.frame_levels(nlevels)
-    E_ref = L.f32(E_ref, 16)
-    s2w, c = pose_camera(list(vol.params.Kinv), E_ref)
-    stream = C.c_void_p(vol.stream)
-    sizes = {"depth": 2 * n, "m_point": 12 * n, "m_normal": 12 * n, "m_flags": n, "words": 8 * L.ICP_WORDS}
-    for l, g in enumerate(geo):
-        m = g["width"] * g["height"]
-        sizes.update({f"z{l}": 4 * m, f"vertex{l}": 12 * m, f"normal{l}": 12 * m, f"flags{l}": m})
-    bufs = {}
-    try:
-        for k, size in sizes.items():
-            bufs[k] = DeviceBuffer(size)
-        vol.render_maps_dev(s2w, c, int(min_weight), point=bufs["m_point"].ptr, normal=bufs["m_normal"].ptr,
-                            flags=bufs["m_flags"].ptr)
-        bufs["depth"].upload(d, stream)
-        vol.frame_pyramid_dev(bufs["depth"].ptr, [{k: bufs[f"{k}{l}"].ptr for k in ("z", "vertex", "normal", "flags")}
-                                                  for l in range(nlevels)], radius, sigma_r, band)
-        model = [bufs[k].ptr for k in ("m_point", "m_normal", "m_flags")]
-        words = np.zeros(L.ICP_WORDS, np.int64)
-
-        def system(level, E, dist_max, cos_min):
-            frame = [bufs[f"{k}{level}"].ptr for k in ("vertex", "normal", "flags")]
-            vol.icp_system_level_dev(frame + model, geo[level]["width"], geo[level]["height"], E_ref, E, dist_max,
-                                     cos_min, stride, bufs["words"].ptr)
-            bufs["words"].download(words, stream)
-            vol.sync()
-            return words
-
-        dims = [(g["width"], g["height"]) for g in geo]
-        return pyramid_loop(system, dims, E0, schedule, stride, min_inliers, eps)
-    finally:
-        vol.sync()
-        for b in bufs.values():
-            b.free()
-
-
-PHOTO_SCALE = 2.0 ** -20    # one unit of the photometric sums
-PHOTO_COUNT_NAMES = ("inliers", "far", "outlier", "none")
-PHOTO_WEIGHT = 0.02         # metres per unit of intensity (DESIGN section 14: the sweep that chose it)
-R_MAX = 0.25                # the gate on the intensity residual, intensities in [0, 1)
-
-
-def rgbd_system_from_words(words):
-    """Two (A, b, r2, counts) tuples of the 64 int64 words: the point-to-plane system as
-    system_from_words returns it (scale 2^-32, metres) and the photometric one (scale 2^-20, units of
-    intensity; counts inliers, far, outlier, none)."""
-    w = np.asarray(words, np.int64).reshape(L.RGBD_WORDS)
-    p = w[L.ICP_WORDS:]
-    A = np.zeros((6, 6), np.float64)
-    A[np.triu_indices(6)] = p[:21].astype(np.float64) * PHOTO_SCALE
-    A = A + np.triu(A, 1).T
-    b = p[21:27].astype(np.float64) * PHOTO_SCALE
-    counts = {n: int(p[28 + k]) for k, n in enumerate(PHOTO_COUNT_NAMES)}
-    return system_from_words(w[:L.ICP_WORDS]), (A, b, float(p[27]) * PHOTO_SCALE, counts)
+    schedule entry runs track_loop's iterations from the previous entry's result, with
+    default_min_inliers of its level's grid unless min_inliers is given.  Returns (E, log); every log
+    entry carries its `level`.  TrackingLost carries the estimate reached and the log of all levels so
+    far, its message the level."""
+    return _loop(system, *_levels(schedule, dims, stride, min_inliers), E0, eps)
 
 
 def rgbd_loop(system, dims, E0, schedule=PYRAMID_SCHEDULE, photo_weight=PHOTO_WEIGHT, r_max=R_MAX, stride=1,
@@ -284,31 +206,124 @@ def rgbd_loop(system, dims, E0, schedule=PYRAMID_SCHEDULE, photo_weight=PHOTO_WE
     (photo_used False in its log entry).  The step, the stop rule and TrackingLost (on the geometric
     inliers alone) are track_loop's.  Log entries are pyramid_loop's plus photo_inliers, photo_rms
     (intensity units, before the step) and photo_used."""
-    E = np.asarray(E0, np.float32).reshape(4, 4).copy()
-    w2 = float(photo_weight) ** 2
-    log = []
-    for level, iters, dist_max, cos_min in schedule:
-        level = int(level)
-        w, h = dims[level]
-        need = default_min_inliers(w, h, int(stride)) if min_inliers is None else min_inliers
-        for it in range(int(iters)):
-            (A, b, r2, counts), (Ap, bp, rp2, pc) = rgbd_system_from_words(system(level, E, dist_max, cos_min, r_max))
-            n, m = counts["inliers"], pc["inliers"]
-            used = m >= need and w2 > 0.0
-            entry = dict(counts, iter=it, rms=math.sqrt(r2 / n) if n else float("nan"), step=float("nan"), level=level,
-                         photo_inliers=m, photo_rms=math.sqrt(rp2 / m) if m else float("nan"), photo_used=used)
-            log.append(entry)
-            if n < need:
-                raise TrackingLost(f"level {level}: iteration {it}: {n} inliers, fewer than {need}", E, log)
-            try:
-                xi = solve_step(A + w2 * Ap, b + w2 * bp) if used else solve_step(A, b)
-            except np.linalg.LinAlgError as e:
-                raise TrackingLost(f"level {level}: iteration {it}: {e}", E, log) from e
-            entry["step"] = float(np.linalg.norm(xi))
-            E = se3_apply(xi, E)
-            if entry["step"] < eps:
-                break
-    return E, log
+    return _loop(lambda level, E, dist_max, cos_min: system(level, E, dist_max, cos_min, r_max),
+                 *_levels(schedule, dims, stride, min_inliers), E0, eps, w2=float(photo_weight) ** 2)
+
+
+@contextlib.contextmanager
+def _device_frame(vol, depth, E_ref, min_weight, sizes, nwords, after_model=None):
+    """The device side that every tracker sets up once per frame, as a context: the buffers named in
+    `sizes` (bytes) beside depth, the three model maps and `nwords` int64 words; the model maps rendered
+    at pose_camera(Kinv, E_ref) (min_weight: their validity threshold); after_model(bufs, s2w, c) if
+    given; the depth (u16, contiguous) uploaded.  Yields (bufs, read_words): the DeviceBuffer table and
+    a function that copies the words into one host array, waits and returns it.  On the way out, also
+    when an allocation fails half way, it waits for the volume's stream and frees every buffer."""
+    from .maps import pose_camera
+    from .volume import DeviceBuffer
+
+    n = vol.W * vol.H
+    s2w, c = pose_camera(list(vol.params.Kinv), E_ref)
+    stream = C.c_void_p(vol.stream)
+    sizes = dict({"depth": 2 * n, "m_point": 12 * n, "m_normal": 12 * n, "m_flags": n, "words": 8 * nwords}, **sizes)
+    bufs = {}
+    try:
+        for k, size in sizes.items():
+            bufs[k] = DeviceBuffer(size)
+        vol.render_maps_dev(s2w, c, int(min_weight), point=bufs["m_point"].ptr, normal=bufs["m_normal"].ptr,
+                            flags=bufs["m_flags"].ptr)
+        if after_model is not None:
+            after_model(bufs, s2w, c)
+        bufs["depth"].upload(depth, stream)
+        words = np.zeros(nwords, np.int64)
+
+        def read_words():
+            bufs["words"].download(words, stream)
+            vol.sync()
+            return words
+
+        yield bufs, read_words
+    finally:
+        vol.sync()
+        for b in bufs.values():
+            b.free()
+
+
+def _level_sizes(geo, per):
+    """{name + level: bytes} of per-pixel buffers on every level of frame_levels' geometry."""
+    return {f"{k}{l}": size * g["width"] * g["height"] for l, g in enumerate(geo) for k, size in per.items()}
+
+
+def _level_pointers(bufs, names, level, keys=None):
+    """The raw pointers of one level's buffers, as a list or under `keys`."""
+    ptrs = [bufs[f"{k}{level}"].ptr for k in names]
+    return dict(zip(keys, ptrs)) if keys else ptrs
+
+
+_LEVEL_MAPS = {"z": 4, "vertex": 12, "normal": 12, "flags": 1}     # bytes per pixel of a depth-pyramid level
+_LEVEL_INTENSITIES = {"fS": 4, "fV": 1, "mS": 4, "mV": 1}         # and of the two intensity pyramids' level
+_MODEL = ("m_point", "m_normal", "m_flags")
+
+
+def _pyramid_args(vol, schedule):
+    """(schedule as tuples, number of levels its coarsest entry needs, their geometry)."""
+    schedule = tuple(tuple(s) for s in schedule)
+    if not schedule or min(int(s[0]) for s in schedule) < 0:
+        raise ValueError("schedule: (level, iterations, dist_max, cos_min) entries with level >= 0")
+    nlevels = max(int(s[0]) for s in schedule) + 1
+    return schedule, nlevels, vol.frame_levels(nlevels)
+
+
+def track(vol, depth, E_ref, E0, iters=10, dist_max=0.1, cos_min=0.8, stride=1, min_weight=1, min_inliers=None,
+          eps=STEP_EPS):
+    """Tracks the depth image (u16 [H, W]) against the model in `vol`, starting from the extrinsic
+    E0.  The model maps are rendered once at pose_camera(Kinv, E_ref) (min_weight: the maps'
+    validity threshold) and stay on the device, as do the frame maps; each iteration is one
+    launch and a 256-byte read-back.  min_inliers defaults to default_min_inliers.  Returns
+    (E, log) as track_loop does, and raises TrackingLost like it."""
+    d = np.ascontiguousarray(depth, dtype=np.uint16)
+    n = vol.W * vol.H
+    if d.size != n:
+        raise ValueError(f"depth must be {vol.H}x{vol.W} u16")
+    if min_inliers is None:
+        min_inliers = default_min_inliers(vol.W, vol.H, int(stride))
+    E_ref = L.f32(E_ref, 16)
+    with _device_frame(vol, d, E_ref, min_weight, {"vertex": 12 * n, "normal": 12 * n, "flags": n},
+                       L.ICP_WORDS) as (bufs, read_words):
+        vol.frame_maps_dev(bufs["depth"].ptr, bufs["vertex"].ptr, bufs["normal"].ptr, bufs["flags"].ptr)
+        pointers = [bufs[k].ptr for k in ("vertex", "normal", "flags") + _MODEL]
+
+        def system(E):
+            vol.icp_system_dev(pointers, E_ref, E, dist_max, cos_min, stride, bufs["words"].ptr)
+            return read_words()
+
+        return track_loop(system, E0, iters, min_inliers, eps)
+
+
+def track_pyramid(vol, depth, E_ref, E0, schedule=PYRAMID_SCHEDULE, radius=3, sigma_r=0.05, band=None, stride=1,
+                  min_weight=1, min_inliers=None, eps=STEP_EPS):
+    """track() coarse to fine on the depth pyramid (Volume.frame_pyramid_dev: the edge-preserving
+    filter of `radius`, `sigma_r`, halvings within `band`).  The model maps are rendered once at full
+    resolution and the pyramid is built once, as many levels as the schedule's coarsest entry needs;
+    everything stays on the device and each iteration is one launch (icp_system_level_dev) and a
+    256-byte read-back.  Returns (E, log) as pyramid_loop does, and raises TrackingLost like it."""
+    d = np.ascontiguousarray(depth, dtype=np.uint16)
+    if d.size != vol.W * vol.H:
+        raise ValueError(f"depth must be {vol.H}x{vol.W} u16")
+    schedule, nlevels, geo = _pyramid_args(vol, schedule)
+    E_ref = L.f32(E_ref, 16)
+    with _device_frame(vol, d, E_ref, min_weight, _level_sizes(geo, _LEVEL_MAPS), L.ICP_WORDS) as (bufs, read_words):
+        vol.frame_pyramid_dev(bufs["depth"].ptr, [_level_pointers(bufs, _LEVEL_MAPS, l, _LEVEL_MAPS) for l in range(nlevels)],
+                              radius, sigma_r, band)
+        model = [bufs[k].ptr for k in _MODEL]
+
+        def system(level, E, dist_max, cos_min):
+            frame = _level_pointers(bufs, ("vertex", "normal", "flags"), level)
+            vol.icp_system_level_dev(frame + model, geo[level]["width"], geo[level]["height"], E_ref, E, dist_max,
+                                     cos_min, stride, bufs["words"].ptr)
+            return read_words()
+
+        dims = [(g["width"], g["height"]) for g in geo]
+        return pyramid_loop(system, dims, E0, schedule, stride, min_inliers, eps)
 
 
 def track_rgbd(vol, depth, rgb, E_ref, E0, schedule=PYRAMID_SCHEDULE, photo_weight=PHOTO_WEIGHT, r_max=R_MAX, radius=3,
@@ -319,66 +334,43 @@ def track_rgbd(vol, depth, rgb, E_ref, E0, schedule=PYRAMID_SCHEDULE, photo_weig
     render (valid where the model flags are 3); then per iteration one launch
     (Volume.rgbd_system_level_dev) and a 512-byte read-back.  Returns (E, log) as rgbd_loop does, and
     raises TrackingLost like it."""
-    from .maps import pose_camera
-    from .volume import DeviceBuffer
-
     d = np.ascontiguousarray(depth, dtype=np.uint16)
     c = np.ascontiguousarray(rgb, dtype=np.uint8)
     n = vol.W * vol.H
     if d.size != n or c.size != 3 * n:
         raise ValueError(f"depth must be {vol.H}x{vol.W} u16 and rgb {vol.H}x{vol.W}x3 u8")
-    schedule = tuple(tuple(s) for s in schedule)
-    if not schedule or min(int(s[0]) for s in schedule) < 0:
-        raise ValueError("schedule: (level, iterations, dist_max, cos_min) entries with level >= 0")
-    nlevels = max(int(s[0]) for s in schedule) + 1
-    geo = vol.frame_levels(nlevels)
+    schedule, nlevels, geo = _pyramid_args(vol, schedule)
     E_ref = L.f32(E_ref, 16)
-    s2w, cam = pose_camera(list(vol.params.Kinv), E_ref)
     stream = C.c_void_p(vol.stream)
-    sizes = {"depth": 2 * n, "rgb": 3 * n, "m_rgb": 3 * n, "m_point": 12 * n, "m_normal": 12 * n, "m_flags": n,
-             "m_valid": n, "words": 8 * L.RGBD_WORDS}
-    for l, g in enumerate(geo):
-        m = g["width"] * g["height"]
-        sizes.update({f"z{l}": 4 * m, f"vertex{l}": 12 * m, f"normal{l}": 12 * m, f"flags{l}": m,
-                      f"fS{l}": 4 * m, f"fV{l}": m, f"mS{l}": 4 * m, f"mV{l}": m})
-    bufs = {}
-    try:
-        for k, size in sizes.items():
-            bufs[k] = DeviceBuffer(size)
-        vol.render_maps_dev(s2w, cam, int(min_weight), point=bufs["m_point"].ptr, normal=bufs["m_normal"].ptr,
-                            flags=bufs["m_flags"].ptr)
+
+    m_flags = np.zeros(n, np.uint8)
+    m_valid = np.zeros(n, np.uint8)   # lives as long as the call: its upload is asynchronous
+
+    def colour_render(bufs, s2w, cam):
         vol.raycast_dev(s2w, cam, L.RENDER_COLOR, bufs["m_rgb"].ptr, stream=stream)
-        m_flags = np.zeros(n, np.uint8)   # the one read-back before the loop: valid = (m_flags & 3) == 3
-        bufs["m_flags"].download(m_flags, stream)
+        bufs["m_flags"].download(m_flags, stream)   # the one read-back before the loop: valid = (m_flags & 3) == 3
         vol.sync()
-        m_valid = np.ascontiguousarray((m_flags & 3) == 3, dtype=np.uint8)
+        m_valid[:] = (m_flags & 3) == 3
         bufs["m_valid"].upload(m_valid, stream)
-        bufs["depth"].upload(d, stream)
+
+    sizes = dict({"rgb": 3 * n, "m_rgb": 3 * n, "m_valid": n}, **_level_sizes(geo, {**_LEVEL_MAPS, **_LEVEL_INTENSITIES}))
+    with _device_frame(vol, d, E_ref, min_weight, sizes, L.RGBD_WORDS, colour_render) as (bufs, read_words):
         bufs["rgb"].upload(c, stream)
-        vol.frame_pyramid_dev(bufs["depth"].ptr, [{k: bufs[f"{k}{l}"].ptr for k in ("z", "vertex", "normal", "flags")}
-                                                  for l in range(nlevels)], radius, sigma_r, band)
-        vol.intensity_pyramid_dev(bufs["rgb"].ptr, None, [{"S": bufs[f"fS{l}"].ptr, "valid": bufs[f"fV{l}"].ptr}
-                                                          for l in range(nlevels)])
-        vol.intensity_pyramid_dev(bufs["m_rgb"].ptr, bufs["m_valid"].ptr,
-                                  [{"S": bufs[f"mS{l}"].ptr, "valid": bufs[f"mV{l}"].ptr} for l in range(nlevels)])
-        model = [bufs[k].ptr for k in ("m_point", "m_normal", "m_flags")]
-        words = np.zeros(L.RGBD_WORDS, np.int64)
+        vol.frame_pyramid_dev(bufs["depth"].ptr, [_level_pointers(bufs, _LEVEL_MAPS, l, _LEVEL_MAPS) for l in range(nlevels)],
+                              radius, sigma_r, band)
+        for image, valid, names in ((bufs["rgb"].ptr, None, ("fS", "fV")), (bufs["m_rgb"].ptr, bufs["m_valid"].ptr, ("mS", "mV"))):
+            vol.intensity_pyramid_dev(image, valid, [_level_pointers(bufs, names, l, ("S", "valid")) for l in range(nlevels)])
+        model = [bufs[k].ptr for k in _MODEL]
 
         def system(level, E, dist_max, cos_min, r_max):
-            frame = [bufs[f"{k}{level}"].ptr for k in ("vertex", "normal", "flags")]
-            photo = [bufs[f"{k}{level}"].ptr for k in ("fS", "fV", "mS", "mV")]
+            frame = _level_pointers(bufs, ("vertex", "normal", "flags"), level)
+            photo = _level_pointers(bufs, _LEVEL_INTENSITIES, level)
             vol.rgbd_system_level_dev(frame + model, photo, level, E_ref, E, dist_max, cos_min, r_max, stride,
                                       bufs["words"].ptr)
-            bufs["words"].download(words, stream)
-            vol.sync()
-            return words
+            return read_words()
 
         dims = [(g["width"], g["height"]) for g in geo]
         return rgbd_loop(system, dims, E0, schedule, photo_weight, r_max, stride, min_inliers, eps)
-    finally:
-        vol.sync()
-        for b in bufs.values():
-            b.free()
 
 
 def pose_errors(E, E_true):

@@ -299,33 +299,51 @@ class Volume:
                                                                                     for p in (vertex, normal, flags)],
                                                 stream))
 
+    def _system(self, fn, maps, photo, grid, E_ref, E_cur, gates, stride, words_ptr=None, stream=None, sizes=None,
+                error=None):
+        """One call of a tracking-system entry point `fn`: `maps` the six maps in semtsdf_icp_in order
+        (frame vertex, normal, flags; model point, normal, flags), `photo` the four intensity arrays
+        in semtsdf_rgbd_in order or None, `grid` the integers the entry point takes between the inputs
+        and the extrinsics (the frame grid or the level), `gates` its thresholds.  With `sizes` the
+        host form: arrays, each of that many elements or ValueError(error), and the words are
+        returned.  Without it the device form: raw pointers and `words_ptr`, nothing is read back."""
+        ins = list(maps) + list(photo or ())
+        words = None
+        if sizes is not None:
+            ins = [np.ascontiguousarray(a, t) for a, t in zip(ins, (np.float32, np.float32, np.uint8) * 2
+                                                               + (np.uint32, np.uint8) * 2)]
+            if any(a.size != size for a, size in zip(ins, sizes)):
+                raise ValueError(error)
+            words = np.zeros(L.RGBD_WORDS if photo else L.ICP_WORDS, np.int64)
+            addrs, wp = [a.ctypes.data for a in ins], L.ptr(words)
+        else:
+            addrs, wp = [int(p) if p else None for p in ins], C.c_void_p(words_ptr) if words_ptr else None
+        structs = [C.byref(L.IcpIn(*addrs[:6]))] + ([C.byref(L.RgbdIn(*addrs[6:]))] if photo else [])
+        er, ec = L.f32(E_ref, 16), L.f32(E_cur, 16)
+        L.check(fn(self._h, *structs, *[int(g) for g in grid], L.ptr(er), L.ptr(ec), *[float(g) for g in gates],
+                   int(stride), wp, stream))
+        return words
+
+    @staticmethod
+    def _maps(frame: dict, model: dict) -> list:
+        return [frame["vertex"], frame["normal"], frame["flags"], model["point"], model["normal"], model["flags"]]
+
     def icp_system(self, frame: dict, model: dict, E_ref, E_cur, dist_max: float = 0.1, cos_min: float = 0.8,
                    stride: int = 1) -> np.ndarray:
         """The 32 int64 words of one ICP iteration's point-to-plane system (semtsdf_icp_system) from
         host arrays: `frame` as frame_maps returns it, `model` the point, normal, flags of
         render_maps at pose_camera(Kinv, E_ref)."""
         n = self.W * self.H
-        arrs = [np.ascontiguousarray(frame["vertex"], np.float32), np.ascontiguousarray(frame["normal"], np.float32),
-                np.ascontiguousarray(frame["flags"], np.uint8), np.ascontiguousarray(model["point"], np.float32),
-                np.ascontiguousarray(model["normal"], np.float32), np.ascontiguousarray(model["flags"], np.uint8)]
-        for a, ch in zip(arrs, (3, 3, 1, 3, 3, 1)):
-            if a.size != n * ch:
-                raise ValueError(f"maps must be {self.H}x{self.W}")
-        words = np.zeros(L.ICP_WORDS, np.int64)
-        er, ec = L.f32(E_ref, 16), L.f32(E_cur, 16)
-        L.check(L.load().semtsdf_icp_system(self._h, C.byref(L.IcpIn(*[a.ctypes.data for a in arrs])), L.ptr(er),
-                                            L.ptr(ec), float(dist_max), float(cos_min), int(stride), L.ptr(words),
-                                            None))
-        return words
+        return self._system(L.load().semtsdf_icp_system, self._maps(frame, model), None, (), E_ref, E_cur,
+                            (dist_max, cos_min), stride, sizes=(n * 3, n * 3, n) * 2,
+                            error=f"maps must be {self.H}x{self.W}")
 
     def icp_system_dev(self, pointers, E_ref, E_cur, dist_max, cos_min, stride, words_ptr: int, stream=None):
         """icp_system on device buffers: `pointers` the six raw pointers in semtsdf_icp_in order
         (frame vertex, normal, flags; model point, normal, flags), `words_ptr` 32 int64 on the
         device; asynchronous on `stream`, nothing is read back."""
-        er, ec = L.f32(E_ref, 16), L.f32(E_cur, 16)
-        L.check(L.load().semtsdf_icp_system_dev(self._h, C.byref(L.IcpIn(*[int(p) if p else None for p in pointers])),
-                                                L.ptr(er), L.ptr(ec), float(dist_max), float(cos_min), int(stride),
-                                                C.c_void_p(words_ptr) if words_ptr else None, stream))
+        self._system(L.load().semtsdf_icp_system_dev, pointers, None, (), E_ref, E_cur, (dist_max, cos_min), stride,
+                     words_ptr, stream)
 
     # ---- depth pyramid (semtsdf/track.py's track_pyramid drives these)
     @staticmethod
@@ -398,29 +416,17 @@ class Volume:
         if fl.ndim != 2:
             raise ValueError("frame flags must be [h, w]")
         fh, fw = fl.shape
-        n = self.W * self.H
-        arrs = [np.ascontiguousarray(frame["vertex"], np.float32), np.ascontiguousarray(frame["normal"], np.float32),
-                fl, np.ascontiguousarray(model["point"], np.float32),
-                np.ascontiguousarray(model["normal"], np.float32), np.ascontiguousarray(model["flags"], np.uint8)]
-        for a, size in zip(arrs, (fw * fh * 3, fw * fh * 3, fw * fh, n * 3, n * 3, n)):
-            if a.size != size:
-                raise ValueError(f"frame maps must be {fh}x{fw}, model maps {self.H}x{self.W}")
-        words = np.zeros(L.ICP_WORDS, np.int64)
-        er, ec = L.f32(E_ref, 16), L.f32(E_cur, 16)
-        L.check(L.load().semtsdf_icp_system_level(self._h, C.byref(L.IcpIn(*[a.ctypes.data for a in arrs])), fw, fh,
-                                                  L.ptr(er), L.ptr(ec), float(dist_max), float(cos_min), int(stride),
-                                                  L.ptr(words), None))
-        return words
+        m, n = fw * fh, self.W * self.H
+        return self._system(L.load().semtsdf_icp_system_level, self._maps(frame, model), None, (fw, fh), E_ref, E_cur,
+                            (dist_max, cos_min), stride, sizes=(m * 3, m * 3, m, n * 3, n * 3, n),
+                            error=f"frame maps must be {fh}x{fw}, model maps {self.H}x{self.W}")
 
     def icp_system_level_dev(self, pointers, frame_width: int, frame_height: int, E_ref, E_cur, dist_max, cos_min,
                              stride, words_ptr: int, stream=None):
         """icp_system_level on device buffers: `pointers` as icp_system_dev takes them, the frame's
         three on a frame_width x frame_height grid; asynchronous on `stream`, nothing is read back."""
-        er, ec = L.f32(E_ref, 16), L.f32(E_cur, 16)
-        L.check(L.load().semtsdf_icp_system_level_dev(
-            self._h, C.byref(L.IcpIn(*[int(p) if p else None for p in pointers])), int(frame_width), int(frame_height),
-            L.ptr(er), L.ptr(ec), float(dist_max), float(cos_min), int(stride),
-            C.c_void_p(words_ptr) if words_ptr else None, stream))
+        self._system(L.load().semtsdf_icp_system_level_dev, pointers, None, (frame_width, frame_height), E_ref, E_cur,
+                     (dist_max, cos_min), stride, words_ptr, stream)
 
     # ---- RGB-D tracking (semtsdf/track.py's track_rgbd drives these)
     def intensity_pyramid(self, rgb, valid=None, nlevels: int = 3) -> list:
@@ -466,34 +472,19 @@ class Volume:
         them (the frame maps of that level), `f_int` and `m_int` that level of intensity_pyramid of the
         frame's colour image and of the model's colour render (dicts with S and valid)."""
         fh, fw = self.H >> int(level), self.W >> int(level)
-        n = self.W * self.H
-        arrs = [np.ascontiguousarray(frame["vertex"], np.float32), np.ascontiguousarray(frame["normal"], np.float32),
-                np.ascontiguousarray(frame["flags"], np.uint8), np.ascontiguousarray(model["point"], np.float32),
-                np.ascontiguousarray(model["normal"], np.float32), np.ascontiguousarray(model["flags"], np.uint8)]
-        ints = [np.ascontiguousarray(f_int["S"], np.uint32), np.ascontiguousarray(f_int["valid"], np.uint8),
-                np.ascontiguousarray(m_int["S"], np.uint32), np.ascontiguousarray(m_int["valid"], np.uint8)]
-        for a, size in zip(arrs + ints, (fw * fh * 3, fw * fh * 3, fw * fh, n * 3, n * 3, n) + (fw * fh,) * 4):
-            if a.size != size:
-                raise ValueError(f"frame maps and intensities must be {fh}x{fw}, model maps {self.H}x{self.W}")
-        words = np.zeros(L.RGBD_WORDS, np.int64)
-        er, ec = L.f32(E_ref, 16), L.f32(E_cur, 16)
-        L.check(L.load().semtsdf_rgbd_system_level(
-            self._h, C.byref(L.IcpIn(*[a.ctypes.data for a in arrs])), C.byref(L.RgbdIn(*[a.ctypes.data for a in ints])),
-            int(level), L.ptr(er), L.ptr(ec), float(dist_max), float(cos_min), float(r_max), int(stride), L.ptr(words),
-            None))
-        return words
+        m, n = fw * fh, self.W * self.H
+        return self._system(L.load().semtsdf_rgbd_system_level, self._maps(frame, model),
+                            [f_int["S"], f_int["valid"], m_int["S"], m_int["valid"]], (level,), E_ref, E_cur,
+                            (dist_max, cos_min, r_max), stride, sizes=(m * 3, m * 3, m, n * 3, n * 3, n) + (m,) * 4,
+                            error=f"frame maps and intensities must be {fh}x{fw}, model maps {self.H}x{self.W}")
 
     def rgbd_system_level_dev(self, pointers, photo, level: int, E_ref, E_cur, dist_max, cos_min, r_max, stride,
                               words_ptr: int, stream=None):
         """rgbd_system_level on device buffers: `pointers` as icp_system_level_dev takes them, `photo`
         the four raw pointers in semtsdf_rgbd_in order (frame S, valid; model S, valid), `words_ptr`
         64 int64 on the device; asynchronous on `stream`, nothing is read back."""
-        er, ec = L.f32(E_ref, 16), L.f32(E_cur, 16)
-        L.check(L.load().semtsdf_rgbd_system_level_dev(
-            self._h, C.byref(L.IcpIn(*[int(p) if p else None for p in pointers])),
-            C.byref(L.RgbdIn(*[int(p) if p else None for p in photo])), int(level), L.ptr(er), L.ptr(ec),
-            float(dist_max), float(cos_min), float(r_max), int(stride), C.c_void_p(words_ptr) if words_ptr else None,
-            stream))
+        self._system(L.load().semtsdf_rgbd_system_level_dev, pointers, photo, (level,), E_ref, E_cur,
+                     (dist_max, cos_min, r_max), stride, words_ptr, stream)
 
     # ---- state transfer (reference layouts)
     def download(self, sdf=True, wt=True, color=True, hist=False, cls=False):

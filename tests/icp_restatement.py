@@ -44,32 +44,72 @@ def restate_frame_maps(depth, Kinv, depth_scale):
     return {"vertex": np.stack(V, axis=-1), "normal": normal, "flags": flags}
 
 
-def restate_system(frame, model, K, E_ref, E_cur, dist_max, cos_min, stride):
-    """The 32 int64 words from the frame maps, the model maps (point, normal, flags), the handle's
-    K (16 values) and the two extrinsics."""
-    H, W = frame["flags"].shape
+def visited_grid(frame, stride):
+    """(ys, xs) of the frame pixels a stride visits, as index grids."""
+    fH, fW = frame["flags"].shape
+    return np.meshgrid(np.arange(0, fH, stride), np.arange(0, fW, stride), indexing="ij")
+
+
+def project(frame, model, K, E_ref, E_cur, ys, xs):
+    """Steps 1-2 of the rule for the frame pixels (ys, xs): (Rt, Pw, q, on, vi, ui) with Rt of E_cur,
+    Pw and q = E_ref Pw as lists of three arrays, `on` where q lies in front of the reference camera and
+    rounds onto the model's grid, and (vi, ui) the model pixel there (0 elsewhere)."""
+    H, W = model["flags"].shape
     K = np.asarray(K, np.float32).reshape(4, 4)
     Er = np.asarray(E_ref, np.float32).reshape(4, 4)
     Ec = np.asarray(E_cur, np.float32).reshape(4, 4)
     Rt = Ec[:3, :3].T
     o = pose_camera_def(np.eye(4, dtype=np.float32).reshape(-1), Ec)[1]  # -Rt t: f64 sums rounded once
-    dmax2 = F(dist_max) * F(dist_max)
-    ys, xs = np.meshgrid(np.arange(0, H, stride), np.arange(0, W, stride), indexing="ij")
-    vis = (frame["flags"][ys, xs] & 3) == 3
-    ys, xs = ys[vis], xs[vis]
     V = [frame["vertex"][ys, xs, a] for a in range(3)]
-    n = [frame["normal"][ys, xs, a] for a in range(3)]
     with np.errstate(all="ignore"):
         Pw = [dot3(Rt[a, 0], Rt[a, 1], Rt[a, 2], V[0], V[1], V[2]) + o[a] for a in range(3)]
-        Nw = [dot3(Rt[a, 0], Rt[a, 1], Rt[a, 2], n[0], n[1], n[2]) for a in range(3)]
         q = [dot3(Er[a, 0], Er[a, 1], Er[a, 2], Pw[0], Pw[1], Pw[2]) + Er[a, 3] for a in range(3)]
         s = [dot3(K[a, 0], K[a, 1], K[a, 2], q[0], q[1], q[2]) for a in range(3)]
         u = np.floor(s[0] / s[2] + F(0.5))
         v = np.floor(s[1] / s[2] + F(0.5))
         on = ~(q[2] <= 0) & (u >= 0) & (u < F(W)) & (v >= 0) & (v < F(H))
-        ui = np.where(on, u, 0).astype(np.int64)
-        vi = np.where(on, v, 0).astype(np.int64)
-        on &= (model["flags"][vi, ui] & 3) == 3
+    ui = np.where(on, u, 0).astype(np.int64)
+    vi = np.where(on, v, 0).astype(np.int64)
+    return Rt, Pw, q, on, vi, ui
+
+
+def pack_words(J, r, inl, far, third, visited, scale):
+    """The 32 int64 words of a system: the sums of RN(x y scale) over the inliers, x y formed in
+    float64, in the order J^T J (upper triangle, row-major), J^T r, r r; then the counts of inliers, far,
+    the third class (angle or outlier) and none = visited less those three."""
+    words = np.zeros(ICP_WORDS, np.int64)
+    t = [j[inl].astype(np.float64) for j in J] + [r[inl].astype(np.float64)]
+
+    def fix(a, b):
+        return int(np.rint(a * b * scale).astype(np.int64).sum())
+
+    w = 0
+    for i in range(6):
+        for j in range(i, 6):
+            words[w] = fix(t[i], t[j])
+            w += 1
+    for i in range(7):
+        words[21 + i] = fix(t[i], t[6])
+    words[28] = int(inl.sum())
+    words[29] = int(far.sum())
+    words[30] = int(third.sum())
+    words[31] = int(visited) - int(words[28] + words[29] + words[30])
+    return words
+
+
+def restate_system_level(frame, model, K, E_ref, E_cur, dist_max, cos_min, stride):
+    """The 32 int64 words from the frame maps, the model maps (point, normal, flags), the handle's K
+    (16 values) and the two extrinsics, on two grids: the visited pixels and the frame maps' shape are
+    the frame's, the projection's bounds and the looked-up maps the model's (the handle's W x H)."""
+    dmax2 = F(dist_max) * F(dist_max)
+    ys, xs = visited_grid(frame, stride)
+    vis = (frame["flags"][ys, xs] & 3) == 3
+    ys, xs = ys[vis], xs[vis]
+    Rt, Pw, _, on, vi, ui = project(frame, model, K, E_ref, E_cur, ys, xs)
+    n = [frame["normal"][ys, xs, a] for a in range(3)]
+    with np.errstate(all="ignore"):
+        Nw = [dot3(Rt[a, 0], Rt[a, 1], Rt[a, 2], n[0], n[1], n[2]) for a in range(3)]
+        on = on & ((model["flags"][vi, ui] & 3) == 3)
         Pm = [model["point"][vi, ui, a] for a in range(3)]
         Nm = [model["normal"][vi, ui, a] for a in range(3)]
         d = [Pm[a] - Pw[a] for a in range(3)]
@@ -80,26 +120,13 @@ def restate_system(frame, model, K, E_ref, E_cur, dist_max, cos_min, stride):
         inl = on & ~far & ~angle
         for k in range(6):
             inl &= np.abs(J[k]) < F(32.0)
-    words = np.zeros(ICP_WORDS, np.int64)
-    J64 = [j[inl].astype(np.float64) for j in J]
-    r64 = r[inl].astype(np.float64)
+    return pack_words(J, r, inl, far, angle, vis.sum(), 4294967296.0)
 
-    def fix(a, b):
-        return int(np.rint(a * b * 4294967296.0).astype(np.int64).sum())
 
-    w = 0
-    for i in range(6):
-        for j in range(i, 6):
-            words[w] = fix(J64[i], J64[j])
-            w += 1
-    for i in range(6):
-        words[21 + i] = fix(J64[i], r64)
-    words[27] = fix(r64, r64)
-    words[28] = int(inl.sum())
-    words[29] = int(far.sum())
-    words[30] = int(angle.sum())
-    words[31] = int(vis.sum()) - int(words[28] + words[29] + words[30])
-    return words
+def restate_system(frame, model, K, E_ref, E_cur, dist_max, cos_min, stride):
+    """restate_system_level with the frame maps on the model's own grid."""
+    assert frame["flags"].shape == model["flags"].shape
+    return restate_system_level(frame, model, K, E_ref, E_cur, dist_max, cos_min, stride)
 
 
 # ------------------------------------------------------------------------------------

@@ -146,63 +146,7 @@ def restate_pyramid(depth, K, Kinv, depth_scale, nlevels, radius, sigma_r, band,
     return out
 
 
-def restate_system_level(frame, model, K, E_ref, E_cur, dist_max, cos_min, stride):
-    """icp_restatement.restate_system with two grids: the visited pixels and the frame maps' shape are
-    the frame's, the projection's bounds and the looked-up maps the model's (the handle's W x H)."""
-    fH, fW = frame["flags"].shape
-    H, W = model["flags"].shape
-    K = np.asarray(K, np.float32).reshape(4, 4)
-    Er = np.asarray(E_ref, np.float32).reshape(4, 4)
-    Ec = np.asarray(E_cur, np.float32).reshape(4, 4)
-    Rt = Ec[:3, :3].T
-    o = pose_camera_def(np.eye(4, dtype=np.float32).reshape(-1), Ec)[1]
-    dmax2 = F(dist_max) * F(dist_max)
-    ys, xs = np.meshgrid(np.arange(0, fH, stride), np.arange(0, fW, stride), indexing="ij")
-    vis = (frame["flags"][ys, xs] & 3) == 3
-    ys, xs = ys[vis], xs[vis]
-    V = [frame["vertex"][ys, xs, a] for a in range(3)]
-    n = [frame["normal"][ys, xs, a] for a in range(3)]
-    with np.errstate(all="ignore"):
-        Pw = [dot3(Rt[a, 0], Rt[a, 1], Rt[a, 2], V[0], V[1], V[2]) + o[a] for a in range(3)]
-        Nw = [dot3(Rt[a, 0], Rt[a, 1], Rt[a, 2], n[0], n[1], n[2]) for a in range(3)]
-        q = [dot3(Er[a, 0], Er[a, 1], Er[a, 2], Pw[0], Pw[1], Pw[2]) + Er[a, 3] for a in range(3)]
-        s = [dot3(K[a, 0], K[a, 1], K[a, 2], q[0], q[1], q[2]) for a in range(3)]
-        u = np.floor(s[0] / s[2] + F(0.5))
-        v = np.floor(s[1] / s[2] + F(0.5))
-        on = ~(q[2] <= 0) & (u >= 0) & (u < F(W)) & (v >= 0) & (v < F(H))
-        ui = np.where(on, u, 0).astype(np.int64)
-        vi = np.where(on, v, 0).astype(np.int64)
-        on &= (model["flags"][vi, ui] & 3) == 3
-        Pm = [model["point"][vi, ui, a] for a in range(3)]
-        Nm = [model["normal"][vi, ui, a] for a in range(3)]
-        d = [Pm[a] - Pw[a] for a in range(3)]
-        far = on & (dot3(d[0], d[1], d[2], d[0], d[1], d[2]) > dmax2)
-        angle = on & ~far & (dot3(Nm[0], Nm[1], Nm[2], Nw[0], Nw[1], Nw[2]) < F(cos_min))
-        r = dot3(Nm[0], Nm[1], Nm[2], d[0], d[1], d[2])
-        J = I.cross(Pw, Nm) + Nm
-        inl = on & ~far & ~angle
-        for k in range(6):
-            inl &= np.abs(J[k]) < F(32.0)
-    words = np.zeros(I.ICP_WORDS, np.int64)
-    J64 = [j[inl].astype(np.float64) for j in J]
-    r64 = r[inl].astype(np.float64)
-
-    def fix(a, b):
-        return int(np.rint(a * b * 4294967296.0).astype(np.int64).sum())
-
-    w = 0
-    for i in range(6):
-        for j in range(i, 6):
-            words[w] = fix(J64[i], J64[j])
-            w += 1
-    for i in range(6):
-        words[21 + i] = fix(J64[i], r64)
-    words[27] = fix(r64, r64)
-    words[28] = int(inl.sum())
-    words[29] = int(far.sum())
-    words[30] = int(angle.sum())
-    words[31] = int(vis.sum()) - int(words[28] + words[29] + words[30])
-    return words
+restate_system_level = I.restate_system_level   # the system with a frame grid of its own: one rule, stated there
 
 
 # ------------------------------------------------------------------------------------

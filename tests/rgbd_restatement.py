@@ -57,28 +57,16 @@ def restate_photo_words(frame, model, f_int, m_int, level, K, E_ref, E_cur, dist
     H, W = model["flags"].shape
     assert (fH, fW) == (H >> level, W >> level) == f_int["S"].shape == m_int["S"].shape
     fxl, fyl, cxl, cyl = level_camera(K, level)
-    K = np.asarray(K, np.float32).reshape(4, 4)
     Er = np.asarray(E_ref, np.float32).reshape(4, 4)
-    Ec = np.asarray(E_cur, np.float32).reshape(4, 4)
-    Rt = Ec[:3, :3].T
-    o = pose_camera_def(np.eye(4, dtype=np.float32).reshape(-1), Ec)[1]
     dmax2 = F(dist_max) * F(dist_max)
     scale = F(2.0 ** -(14 + 2 * level))
-    ys, xs = np.meshgrid(np.arange(0, fH, stride), np.arange(0, fW, stride), indexing="ij")
+    ys, xs = I.visited_grid(frame, stride)
     vis = ((frame["flags"][ys, xs] & 1) != 0) & (f_int["valid"][ys, xs] != 0)
     ys, xs = ys[vis], xs[vis]
-    V = [frame["vertex"][ys, xs, a] for a in range(3)]
+    _, Pw, q, on, vi, ui = I.project(frame, model, K, E_ref, E_cur, ys, xs)
     mS, mV = m_int["S"], m_int["valid"]
     with np.errstate(all="ignore"):
-        Pw = [dot3(Rt[a, 0], Rt[a, 1], Rt[a, 2], V[0], V[1], V[2]) + o[a] for a in range(3)]
-        q = [dot3(Er[a, 0], Er[a, 1], Er[a, 2], Pw[0], Pw[1], Pw[2]) + Er[a, 3] for a in range(3)]
-        s = [dot3(K[a, 0], K[a, 1], K[a, 2], q[0], q[1], q[2]) for a in range(3)]
-        u = np.floor(s[0] / s[2] + F(0.5))
-        v = np.floor(s[1] / s[2] + F(0.5))
-        on = ~(q[2] <= 0) & (u >= 0) & (u < F(W)) & (v >= 0) & (v < F(H))
-        ui = np.where(on, u, 0).astype(np.int64)
-        vi = np.where(on, v, 0).astype(np.int64)
-        on &= (model["flags"][vi, ui] & 1) != 0
+        on = on & ((model["flags"][vi, ui] & 1) != 0)
         d = [model["point"][vi, ui, a] - Pw[a] for a in range(3)]
         far = on & (dot3(d[0], d[1], d[2], d[0], d[1], d[2]) > dmax2)
         iz = F(1.0) / q[2]
@@ -112,26 +100,7 @@ def restate_photo_words(frame, model, f_int, m_int, level, K, E_ref, E_cur, dist
         inl = inside & ~outlier
         for k in range(6):
             inl &= np.abs(J[k]) < F(2048.0)
-    words = np.zeros(32, np.int64)
-    J64 = [j[inl].astype(np.float64) for j in J]
-    r64 = r[inl].astype(np.float64)
-
-    def fix(a, b):
-        return int(np.rint(a * b * 1048576.0).astype(np.int64).sum())
-
-    w = 0
-    for i in range(6):
-        for j in range(i, 6):
-            words[w] = fix(J64[i], J64[j])
-            w += 1
-    for i in range(6):
-        words[21 + i] = fix(J64[i], r64)
-    words[27] = fix(r64, r64)
-    words[28] = int(inl.sum())
-    words[29] = int(far.sum())
-    words[30] = int(outlier.sum())
-    words[31] = int(vis.sum()) - int(words[28] + words[29] + words[30])
-    return words
+    return I.pack_words(J, r, inl, far, outlier, vis.sum(), 1048576.0)
 
 
 def restate_rgbd_system(frame, model, f_int, m_int, level, K, E_ref, E_cur, dist_max, cos_min, r_max, stride=1):
