@@ -810,6 +810,55 @@ int semtsdf_instance_stats(semtsdf_vol* v, float sdf_max, int32_t min_weight,
 int semtsdf_remap_instances(semtsdf_vol* v, const uint8_t lut[SEMTSDF_MAX_OBJECTS], int32_t num_objs,
                             void* stream);
 
+/* ---- brick paging: occupied bricks out to the host and back (no reference counterpart) ----------
+ * Bricks and voxels.  Brick b = (bx, by, bz), 0 <= b[a] < nb[a] = ceil(dim[a] / 8), holds the voxels
+ *   8 b[a] <= i[a] < 8 b[a] + 8.  A voxel is real iff i[a] < dim[a] on every axis.  Voxel (x, y, z)
+ *   has place w = 64 (x & 7) + 8 (y & 7) + (z & 7) in its brick.
+ * Reset state, occupancy.  The reset state of a voxel is what semtsdf_reset leaves: sdf bits equal to
+ *   those of mu; weight, colour, all 32 histogram bins, cls and cls_cnt 0.  A brick is occupied iff
+ *   some real voxel of it differs from the reset state in any field the volume has (floats compared
+ *   as bits).  bins of a brick is the OR over its real voxels of
+ *   (hist[k] != 0) << k; 0 for a volume without SEMTSDF_F_SEMANTIC.
+ * Record.  The record of a brick is made of u32 planes of 512 words, each in place order w:
+ *   1. sdf bits;  2. weight as i32;
+ *   3. colour: one plane r | g << 8 | b << 16 for u8 volumes, three planes r, g, b as i32 for
+ *      SEMTSDF_F_COLOR_I32 volumes (whatever the current storage form is);
+ *   4. one plane of hist[k] for every set bit k of bins, ascending;
+ *   5. cls, then cls_cnt, for SEMTSDF_F_VOTE volumes.
+ *   Voxels that are not real hold the reset state in the record.  A record does not depend on
+ *   whether weights or colour are currently stored narrow or wide.
+ * semtsdf_pack_bricks: the occupied bricks of the box lo <= b < hi (brick units) in ascending
+ *   (bx, by, bz) order, z fastest; records back to back, offset (in words) the running sum.  A box
+ *   outside 0 <= lo <= hi <= nb: SEMTSDF_ERR_INVALID; an empty box is legal.  Outputs are host
+ *   pointers; the call synchronises.  bricks == NULL && words == NULL: count only (one NULL alone is
+ *   SEMTSDF_ERR_INVALID).  With both given and a capacity short: SEMTSDF_ERR_INVALID, the counts
+ *   written, the buffers untouched.  The volume and its derived state are not modified; the call
+ *   orders itself after the work queued on the handle; two calls on one state return identical bytes.
+ * semtsdf_unpack_bricks: overwrites the real voxels of the listed bricks with their records.  Planes
+ *   of bins not in `bins` become 0, the bin mask is rebuilt per voxel from the written values;
+ *   padding voxels and every other brick stay untouched.  Checked before any device work, each
+ *   SEMTSDF_ERR_INVALID with nothing applied: a coordinate out of range; bricks not strictly
+ *   ascending (so no duplicates); offsets that are not the running sum, or a total other than
+ *   n_words; bins != 0 on a volume without SEMTSDF_F_SEMANTIC.  As semtsdf_upload: it runs after the
+ *   last map update, the volume widens first if a weight does not fit u16 or an i32 colour lies
+ *   outside [0, 255], the bound of the weights is raised (never lowered), the steady flags of every
+ *   touched line are cleared, the empty-space maps are rebuilt before their next use, and the call
+ *   synchronises.  n_bricks == 0 returns at once.
+ * Both: a Z-sharded handle is SEMTSDF_ERR_UNSUPPORTED.  Staging (8 B, and to fill 24 B, per brick
+ *   of the box; at most 256 MiB of records, or one record, at a time) comes from the handle's pool:
+ *   it is counted in device_bytes while the call runs and released before it returns; failing to get
+ *   it is SEMTSDF_ERR_OOM with the volume untouched. */
+typedef struct semtsdf_brick { /* 24 bytes */
+    int32_t b[3];
+    uint32_t bins;
+    uint64_t offset; /* of the record, in words */
+} semtsdf_brick;
+int semtsdf_pack_bricks(semtsdf_vol* v, const int32_t lo[3], const int32_t hi[3], semtsdf_brick* bricks,
+                        uint64_t brick_capacity, uint32_t* words, uint64_t word_capacity, uint64_t* n_bricks,
+                        uint64_t* n_words);
+int semtsdf_unpack_bricks(semtsdf_vol* v, const semtsdf_brick* bricks, uint64_t n_bricks, const uint32_t* words,
+                          uint64_t n_words);
+
 /* ---- empty-space maps (tests) ------------------------------------------------------------
  * The octant distance map of the current volume state, one word per 8^3 brick (x-major, z
  * fastest): byte o = the octant-o distance in bricks (0: the brick is not skippable).  count =

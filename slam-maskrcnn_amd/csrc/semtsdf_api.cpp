@@ -2582,6 +2582,176 @@ int semtsdf_extract_mesh(semtsdf_vol* v, int32_t min_weight, semtsdf_mesh_vertex
     return SEMTSDF_OK;
 }
 
+// Brick paging (DESIGN.md "Paging bricks").  Staging of both calls comes from the handle's pool (it
+// shows in device_bytes while the call runs) and is released on every path by this guard.
+namespace {
+struct PoolStage {
+    semtsdf_vol* v;
+    std::vector<void*> held;
+    explicit PoolStage(semtsdf_vol* vol) : v(vol) {}
+    ~PoolStage() { for (void* p : held) v->pool.release(p); }
+    int alloc(void** p, size_t bytes) {
+        if (int rc = v->pool.alloc(p, bytes)) return rc;
+        if (*p) held.push_back(*p);
+        return SEMTSDF_OK;
+    }
+};
+
+// The bricks [r0, r1) whose records fit one staging trip: at most kBrickChunkWords words, one record at least.
+uint64_t brick_chunk_end(const semtsdf_brick* bricks, uint64_t r0, uint64_t n, uint64_t n_words) {
+    uint64_t r1 = r0 + 1;
+    auto end_of = [&](uint64_t r) { return r + 1 < n ? bricks[r + 1].offset : n_words; };
+    while (r1 < n && end_of(r1) - bricks[r0].offset <= kBrickChunkWords) ++r1;
+    return r1;
+}
+}  // namespace
+
+int semtsdf_pack_bricks(semtsdf_vol* v, const int32_t lo[3], const int32_t hi[3], semtsdf_brick* bricks,
+                        uint64_t brick_capacity, uint32_t* words, uint64_t word_capacity, uint64_t* n_bricks,
+                        uint64_t* n_words) {
+    static_assert(sizeof(semtsdf_brick) == sizeof(BrickRec) && sizeof(BrickRec) == 24, "brick entry layout");
+    if (!v || !lo || !hi || !n_bricks || !n_words) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
+    if (!bricks != !words) return fail(SEMTSDF_ERR_INVALID, "bricks and words must both be given or both be NULL");
+    if (v->g.nshards > 1) return fail(SEMTSDF_ERR_UNSUPPORTED, "semtsdf_pack_bricks: a Z-sharded handle is not supported");
+    const int nb[3] = {v->g.nbx, v->g.nby, v->g.nbz};
+    BrickBox box;
+    for (int a = 0; a < 3; ++a) {
+        if (lo[a] < 0 || lo[a] > hi[a] || hi[a] > nb[a])
+            return fail(SEMTSDF_ERR_INVALID, "brick box [%d, %d) on axis %d outside 0 <= lo <= hi <= %d", lo[a], hi[a], a, nb[a]);
+        box.lo[a] = lo[a];
+        box.n[a] = hi[a] - lo[a];
+    }
+    *n_bricks = *n_words = 0;
+    const uint64_t nbox = (uint64_t)box.n[0] * box.n[1] * box.n[2];
+    if (nbox == 0) return SEMTSDF_OK;
+    HIPC(hipSetDevice(v->device));
+    hipStream_t s = v->stream;
+    if (int rc = after_maps(v, s)) return rc;
+    if (v->prep_stream) HIPC(hipStreamSynchronize(v->prep_stream));
+    const int cwide = v->color_wide ? 1 : 0, ci32 = (v->p.flags & SEMTSDF_F_COLOR_I32) ? 1 : 0;
+    PoolStage stage(v);
+    uint2* info_d = nullptr;
+    BrickRec* list_d = nullptr;
+    unsigned long long* tot_d = nullptr;
+    if (int rc = stage.alloc((void**)&info_d, nbox * sizeof(uint2))) return rc;
+    if (int rc = stage.alloc((void**)&tot_d, 2 * sizeof(unsigned long long))) return rc;
+    if (bricks)
+        if (int rc = stage.alloc((void**)&list_d, nbox * sizeof(BrickRec))) return rc;
+    unsigned long long tot[2] = {0, 0};
+    hipError_t e = launch_brick_occupancy(v->g, v->b, cwide, ci32, box, info_d, s);
+    if (e == hipSuccess) e = launch_brick_scan(box, info_d, list_d, tot_d, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(tot, tot_d, sizeof(tot), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(SEMTSDF_ERR_HIP, "brick occupancy: %s", hipGetErrorString(e));
+    *n_bricks = tot[0];
+    *n_words = tot[1];
+    if (!bricks) return SEMTSDF_OK;
+    if (brick_capacity < tot[0] || word_capacity < tot[1])
+        return fail(SEMTSDF_ERR_INVALID, "%llu bricks of %llu words exceed the capacities %llu, %llu", tot[0], tot[1],
+                    (unsigned long long)brick_capacity, (unsigned long long)word_capacity);
+    if (tot[0] == 0) return SEMTSDF_OK;
+    // the list first (it tells the trips apart), then the records through one staging buffer
+    std::vector<semtsdf_brick> list(tot[0]);
+    e = hipMemcpyAsync(list.data(), list_d, tot[0] * sizeof(BrickRec), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(SEMTSDF_ERR_HIP, "brick list: %s", hipGetErrorString(e));
+    uint64_t most = 0;
+    for (uint64_t r0 = 0; r0 < tot[0];) {
+        const uint64_t r1 = brick_chunk_end(list.data(), r0, tot[0], tot[1]);
+        most = std::max<uint64_t>(most, (r1 < tot[0] ? list[r1].offset : tot[1]) - list[r0].offset);
+        r0 = r1;
+    }
+    uint32_t* words_d = nullptr;
+    if (int rc = stage.alloc((void**)&words_d, most * sizeof(uint32_t))) return rc;
+    for (uint64_t r0 = 0; r0 < tot[0];) {
+        const uint64_t r1 = brick_chunk_end(list.data(), r0, tot[0], tot[1]);
+        const uint64_t w0 = list[r0].offset, w1 = r1 < tot[0] ? list[r1].offset : tot[1];
+        e = launch_brick_records(true, v->g, v->b, cwide, ci32, list_d + r0, r1 - r0, w0, words_d, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(words + w0, words_d, (w1 - w0) * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return fail(SEMTSDF_ERR_HIP, "brick gather: %s", hipGetErrorString(e));
+        r0 = r1;
+    }
+    memcpy(bricks, list.data(), tot[0] * sizeof(semtsdf_brick));
+    return SEMTSDF_OK;
+}
+
+int semtsdf_unpack_bricks(semtsdf_vol* v, const semtsdf_brick* bricks, uint64_t n_bricks, const uint32_t* words,
+                          uint64_t n_words) {
+    if (!v) return fail(SEMTSDF_ERR_INVALID, "NULL handle");
+    if (v->g.nshards > 1) return fail(SEMTSDF_ERR_UNSUPPORTED, "semtsdf_unpack_bricks: a Z-sharded handle is not supported");
+    if (n_bricks == 0) return n_words ? fail(SEMTSDF_ERR_INVALID, "%llu words for no brick", (unsigned long long)n_words)
+                                      : SEMTSDF_OK;
+    if (!bricks || !words) return fail(SEMTSDF_ERR_INVALID, "NULL argument");
+    const int nb[3] = {v->g.nbx, v->g.nby, v->g.nbz};
+    const bool ci32 = v->p.flags & SEMTSDF_F_COLOR_I32, vote = v->p.flags & SEMTSDF_F_VOTE;
+    uint64_t sum = 0;
+    for (uint64_t r = 0; r < n_bricks; ++r) {
+        const semtsdf_brick& k = bricks[r];
+        for (int a = 0; a < 3; ++a)
+            if (k.b[a] < 0 || k.b[a] >= nb[a])
+                return fail(SEMTSDF_ERR_INVALID, "brick %llu: coordinate %d on axis %d outside [0, %d)", (unsigned long long)r,
+                            k.b[a], a, nb[a]);
+        if (r && !std::lexicographical_compare(bricks[r - 1].b, bricks[r - 1].b + 3, k.b, k.b + 3))
+            return fail(SEMTSDF_ERR_INVALID, "brick %llu: bricks must be strictly ascending", (unsigned long long)r);
+        if (k.bins && !(v->p.flags & SEMTSDF_F_SEMANTIC))
+            return fail(SEMTSDF_ERR_INVALID, "brick %llu: histogram bins on a volume without SEMTSDF_F_SEMANTIC", (unsigned long long)r);
+        if (k.offset != sum)
+            return fail(SEMTSDF_ERR_INVALID, "brick %llu: offset %llu, expected %llu", (unsigned long long)r,
+                        (unsigned long long)k.offset, (unsigned long long)sum);
+        sum += brick_record_words(ci32, vote, k.bins);
+        if (sum > n_words) return fail(SEMTSDF_ERR_INVALID, "brick %llu: its record ends past %llu words", (unsigned long long)r,
+                                       (unsigned long long)n_words);
+    }
+    if (sum != n_words)
+        return fail(SEMTSDF_ERR_INVALID, "records of %llu words, %llu given", (unsigned long long)sum, (unsigned long long)n_words);
+    // what the records ask of the storage: the weights' bound and range, colours outside a byte
+    WeightScan ws{0, true};
+    bool color_fits = true;
+    for (uint64_t r = 0; r < n_bricks; ++r) {
+        const uint32_t* rec = words + bricks[r].offset;
+        const WeightScan w = scan_weights(reinterpret_cast<const int32_t*>(rec + kBrickVoxels), kBrickVoxels);
+        ws.wmax = std::max(ws.wmax, w.wmax);
+        ws.fits_u16 = ws.fits_u16 && w.fits_u16;
+        if (ci32 && !v->color_wide)
+            for (int i = 2 * kBrickVoxels; i < 5 * kBrickVoxels && color_fits; ++i) color_fits = rec[i] <= 255u;
+    }
+    HIPC(hipSetDevice(v->device));
+    hipStream_t s = v->stream;
+    if (int rc = after_maps(v, s)) return rc;
+    if (v->prep_stream) HIPC(hipStreamSynchronize(v->prep_stream));
+    uint64_t most = 0;
+    for (uint64_t r0 = 0; r0 < n_bricks;) {
+        const uint64_t r1 = brick_chunk_end(bricks, r0, n_bricks, n_words);
+        most = std::max<uint64_t>(most, (r1 < n_bricks ? bricks[r1].offset : n_words) - bricks[r0].offset);
+        r0 = r1;
+    }
+    PoolStage stage(v);
+    BrickRec* list_d = nullptr;
+    uint32_t* words_d = nullptr;
+    if (int rc = stage.alloc((void**)&list_d, n_bricks * sizeof(BrickRec))) return rc;
+    if (int rc = stage.alloc((void**)&words_d, most * sizeof(uint32_t))) return rc;
+    if (!ws.fits_u16)
+        if (int rc = widen_weights(v, s)) return rc;
+    if (!color_fits)
+        if (int rc = widen_color(v, s)) return rc;
+    // derived state first, as semtsdf_upload (the kernel clears the steady flags of the lines it writes)
+    v->maps_stale = true;
+    v->wmax_bound = std::max<int64_t>(v->wmax_bound, ws.wmax);
+    HIPC(hipMemcpyAsync(list_d, bricks, n_bricks * sizeof(BrickRec), hipMemcpyHostToDevice, s));
+    for (uint64_t r0 = 0; r0 < n_bricks;) {
+        const uint64_t r1 = brick_chunk_end(bricks, r0, n_bricks, n_words);
+        const uint64_t w0 = bricks[r0].offset, w1 = r1 < n_bricks ? bricks[r1].offset : n_words;
+        hipError_t e = hipMemcpyAsync(words_d, words + w0, (w1 - w0) * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess)
+            e = launch_brick_records(false, v->g, v->b, v->color_wide ? 1 : 0, ci32 ? 1 : 0, list_d + r0, r1 - r0, w0, words_d, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return fail(SEMTSDF_ERR_HIP, "brick scatter: %s", hipGetErrorString(e));
+        r0 = r1;
+    }
+    return SEMTSDF_OK;
+}
+
 int semtsdf_instance_stats(semtsdf_vol* v, float sdf_max, int32_t min_weight, semtsdf_instance* out,
                            uint64_t* overlap) {
     static_assert(sizeof(semtsdf_instance) == sizeof(InstanceRec) && sizeof(InstanceRec) == 96, "instance layout");

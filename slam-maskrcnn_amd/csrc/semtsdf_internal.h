@@ -5,6 +5,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "semtsdf_bricks.h"
 #include "semtsdf_shift.h"
 
 namespace semtsdf {
@@ -555,5 +556,25 @@ struct RemapLut {
     unsigned long long w[4];
 };
 hipError_t launch_remap_instances(const VolGeom& g, const VolBufs& b, RemapLut lut, uint32_t moved, hipStream_t s);
+
+// Brick paging (semtsdf_pack_bricks / semtsdf_unpack_bricks; the index rule is semtsdf_bricks.h).
+struct BrickBox {   // lo[a] <= b[a] < lo[a] + n[a], in bricks; output order x-major, z fastest
+    int lo[3], n[3];
+};
+struct BrickRec {   // semtsdf_brick
+    int32_t b[3];
+    uint32_t bins;
+    uint64_t offset;  // words
+};
+constexpr uint64_t kBrickChunkWords = 1ull << 26;  // records staged per trip: 256 MiB, or one record more
+// info: [bricks of the box] {planes of the record, 0 = reset state; bins}
+hipError_t launch_brick_occupancy(const VolGeom& g, const VolBufs& b, int color_wide, int color_i32, const BrickBox& box,
+                                  uint2* info, hipStream_t s);
+// list: the occupied bricks in order with their offsets (nullptr: totals only); totals: {bricks, words}
+hipError_t launch_brick_scan(const BrickBox& box, const uint2* info, BrickRec* list, unsigned long long* totals,
+                             hipStream_t s);
+// the records of list[0 .. n) from (gather) or into the volume; a record starts at words[offset - word0]
+hipError_t launch_brick_records(bool gather, const VolGeom& g, const VolBufs& b, int color_wide, int color_i32,
+                                const BrickRec* list, uint64_t n, uint64_t word0, uint32_t* words, hipStream_t s);
 
 }  // namespace semtsdf

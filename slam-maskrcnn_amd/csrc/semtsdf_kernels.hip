@@ -5660,4 +5660,313 @@ hipError_t launch_remap_instances(const VolGeom& g, const VolBufs& b, RemapLut l
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------
+// semtsdf_pack_bricks / semtsdf_unpack_bricks: the occupied 8^3 bricks of a box as records, and
+// back (include/semtsdf.h, DESIGN.md "Paging bricks").  A brick is 8 runs of 64 consecutive
+// elements (semtsdf_bricks.h); every kernel gives a brick to one wave, lane l on element l of each
+// run, so a load or store instruction covers one whole span: 256 B of a 4-byte array, 128 B of u16
+// weights, 1 KiB of wide colour.  Runs past the last x layer do not exist in the storage: their
+// address is clamped onto the last layer and the lanes are masked like padding voxels.
+// ------------------------------------------------------------------------------------
+struct BrickLanes {
+    int bx, by, bz;
+    uint32_t t[kBrickRuns];  // tiled index of this lane's element in run x (clamped: see above)
+    uint32_t real;           // bit x: this lane's voxel of run x is real
+    uint32_t exists;         // bit x: run x exists
+};
+
+__device__ __forceinline__ BrickLanes brick_lanes(const VolGeom& g, int bx, int by, int bz, int lane) {
+    const BrickGeom bg{g.dimx, g.dimy, g.lz, g.tx, g.ty};
+    BrickLanes L;
+    L.bx = bx; L.by = by; L.bz = bz;
+    L.real = L.exists = 0xFFu;
+    const bool ragged = brick_ragged(bg, bx, by, bz);  // wave-uniform
+    if (ragged) L.real = L.exists = 0u;
+#pragma unroll
+    for (int x = 0; x < kBrickRuns; ++x) {
+        int xc = x;
+        if (ragged) {
+            if (brick_run_exists(bg, bx, x)) L.exists |= 1u << x;
+            else xc = g.dimx - 1 - kBrick * bx;
+            if (brick_voxel_real(bg, bx, by, bz, x, lane)) L.real |= 1u << x;
+        }
+        L.t[x] = brick_run_start(bg, bx, by, bz, xc) + (uint32_t)lane;
+    }
+    return L;
+}
+
+__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
+    for (int off = 32; off > 0; off >>= 1) v |= (uint32_t)__shfl_xor((int)v, off, 64);
+    return v;
+}
+
+// Occupancy: info[i] = {planes of the record (0: the brick holds the reset state), bins} for brick i
+// of the box in output order (x-major, z fastest).  The histogram is judged by the bin mask, which the
+// integrate, the upload and the remap keep equal to (hist[k] != 0) << k.
+template <bool WT_WIDE, bool COL_WIDE>
+__global__ __launch_bounds__(256) void k_brick_occupancy(VolGeom g, VolBufs b, BrickBox box, uint64_t nbox, int color_i32,
+                                                         uint2* __restrict__ info) {
+    const uint64_t i = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (i >= nbox) return;
+    const int lane = threadIdx.x & 63;
+    const uint32_t n12 = (uint32_t)box.n[1] * (uint32_t)box.n[2];
+    const uint32_t ix = (uint32_t)(i / n12), r = (uint32_t)(i - (uint64_t)ix * n12);
+    const BrickLanes L = brick_lanes(g, box.lo[0] + (int)ix, box.lo[1] + (int)(r / (uint32_t)box.n[2]),
+                                     box.lo[2] + (int)(r % (uint32_t)box.n[2]), lane);
+    uint32_t sdf[kBrickRuns], wt[kBrickRuns], col[kBrickRuns], hm[kBrickRuns], cl[kBrickRuns], cc[kBrickRuns];
+    const uint32_t* sdfp = reinterpret_cast<const uint32_t*>(b.sdf);
+    // every load first
+#pragma unroll
+    for (int x = 0; x < kBrickRuns; ++x) {
+        sdf[x] = sdfp[L.t[x]];
+        wt[x] = WT_WIDE ? static_cast<const uint32_t*>(b.wt)[L.t[x]] : (uint32_t)static_cast<const uint16_t*>(b.wt)[L.t[x]];
+        if (COL_WIDE) {
+            const int4 c = static_cast<const int4*>(b.color)[L.t[x]];
+            col[x] = (uint32_t)(c.x | c.y | c.z);
+        } else {
+            col[x] = static_cast<const uint32_t*>(b.color)[L.t[x]] & 0x00FFFFFFu;
+        }
+        hm[x] = b.hmask ? b.hmask[L.t[x]] : 0u;
+        cl[x] = b.cls ? (uint32_t)b.cls[L.t[x]] : 0u;
+        cc[x] = b.cls_cnt ? (uint32_t)b.cls_cnt[L.t[x]] : 0u;
+    }
+    const uint32_t mu_bits = __float_as_uint(g.mu);
+    uint32_t diff = 0, bins = 0;
+#pragma unroll
+    for (int x = 0; x < kBrickRuns; ++x) {
+        const uint32_t keep = (L.real >> x) & 1u ? ~0u : 0u;
+        diff |= ((sdf[x] ^ mu_bits) | wt[x] | col[x] | hm[x] | cl[x] | cc[x]) & keep;
+        bins |= hm[x] & keep;
+    }
+    bins = wave_or(bins);
+    const bool occupied = __any(diff != 0u);
+    if (lane == 0)
+        info[i] = make_uint2(occupied ? (uint32_t)brick_record_planes(color_i32 != 0, b.cls != nullptr, bins) : 0u, bins);
+}
+
+hipError_t launch_brick_occupancy(const VolGeom& g, const VolBufs& b, int color_wide, int color_i32, const BrickBox& box,
+                                  uint2* info, hipStream_t s) {
+    const uint64_t nbox = (uint64_t)box.n[0] * box.n[1] * box.n[2];
+    if (nbox == 0) return hipSuccess;
+    const dim3 gr((unsigned)((nbox + 3) / 4)), bl(256);
+#define SEMTSDF_OCC_LAUNCH(W, C) hipLaunchKernelGGL((k_brick_occupancy<W, C>), gr, bl, 0, s, g, b, box, nbox, color_i32, info)
+    if (b.wt_wide) { if (color_wide) SEMTSDF_OCC_LAUNCH(true, true); else SEMTSDF_OCC_LAUNCH(true, false); }
+    else { if (color_wide) SEMTSDF_OCC_LAUNCH(false, true); else SEMTSDF_OCC_LAUNCH(false, false); }
+#undef SEMTSDF_OCC_LAUNCH
+    return hipGetLastError();
+}
+
+// Ordered compaction: one workgroup walks info in chunks of 4096 bricks (16 per thread), carrying the
+// running brick count and word offset, and writes the entry of every occupied brick at its rank.
+// Each sum is formed in one fixed order, so the result does not depend on timing.
+constexpr int kBrickScanPer = 16;
+__global__ __launch_bounds__(256) void k_brick_scan(BrickBox box, const uint2* __restrict__ info, uint64_t nbox,
+                                                    BrickRec* __restrict__ list, unsigned long long* __restrict__ totals) {
+    __shared__ unsigned long long s_cnt[4], s_wrd[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t n2 = (uint32_t)box.n[2], n12 = (uint32_t)box.n[1] * n2;
+    unsigned long long carry_c = 0, carry_w = 0;  // the same in every thread
+    for (uint64_t base = 0; base < nbox; base += 256u * kBrickScanPer) {
+        const uint64_t i0 = base + (uint64_t)tid * kBrickScanPer;
+        uint2 it[kBrickScanPer];
+        unsigned long long c = 0, w = 0;
+#pragma unroll
+        for (int j = 0; j < kBrickScanPer; ++j) {
+            it[j] = i0 + j < nbox ? info[i0 + j] : make_uint2(0u, 0u);
+            if (it[j].x) { ++c; w += (unsigned long long)it[j].x * kBrickVoxels; }
+        }
+        unsigned long long ic = c, iw = w;  // inclusive over the wave
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned long long oc = __shfl_up(ic, off, 64), ow = __shfl_up(iw, off, 64);
+            if (lane >= off) { ic += oc; iw += ow; }
+        }
+        if (lane == 63) { s_cnt[wave] = ic; s_wrd[wave] = iw; }
+        __syncthreads();
+        unsigned long long ec = carry_c + ic - c, ew = carry_w + iw - w, tc = 0, tw = 0;
+        for (int k = 0; k < 4; ++k) {
+            if (k < wave) { ec += s_cnt[k]; ew += s_wrd[k]; }
+            tc += s_cnt[k];
+            tw += s_wrd[k];
+        }
+        if (list) {
+#pragma unroll
+            for (int j = 0; j < kBrickScanPer; ++j) {
+                if (!it[j].x) continue;
+                const uint64_t i = i0 + j;
+                const uint32_t ix = (uint32_t)(i / n12), r = (uint32_t)(i - (uint64_t)ix * n12);
+                BrickRec rec;
+                rec.b[0] = box.lo[0] + (int)ix;
+                rec.b[1] = box.lo[1] + (int)(r / n2);
+                rec.b[2] = box.lo[2] + (int)(r % n2);
+                rec.bins = it[j].y;
+                rec.offset = ew;
+                list[ec] = rec;
+                ++ec;
+                ew += (unsigned long long)it[j].x * kBrickVoxels;
+            }
+        }
+        carry_c += tc;
+        carry_w += tw;
+        __syncthreads();  // s_cnt / s_wrd are rewritten by the next chunk
+    }
+    if (tid == 0) { totals[0] = carry_c; totals[1] = carry_w; }
+}
+
+hipError_t launch_brick_scan(const BrickBox& box, const uint2* info, BrickRec* list, unsigned long long* totals,
+                             hipStream_t s) {
+    const uint64_t nbox = (uint64_t)box.n[0] * box.n[1] * box.n[2];
+    hipLaunchKernelGGL(k_brick_scan, dim3(1), dim3(256), 0, s, box, info, nbox, list, totals);
+    return hipGetLastError();
+}
+
+// Gather (GATHER) and scatter of the records of the bricks list[0 .. n): a record starts at word
+// list[r].offset - word0 of `words`.  Plane by plane, 8 runs each; the e -> w permutation keeps a
+// run's 64 words inside one 256-B span of the record.
+//   gather:  voxels that are not real take the reset state
+//   scatter: only real voxels are written; histogram planes outside bins become 0, the bin mask word
+//            comes from the values written; the steady flags of the brick's 16 lines are cleared
+template <bool GATHER, bool WT_WIDE, bool COL_WIDE>
+__global__ __launch_bounds__(256) void k_brick_records(VolGeom g, VolBufs b, int color_i32, const BrickRec* __restrict__ list,
+                                                       uint64_t n, uint64_t word0, uint32_t* __restrict__ words) {
+    const uint64_t r = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const int lane = threadIdx.x & 63;
+    const BrickRec rec = list[r];
+    const BrickLanes L = brick_lanes(g, rec.b[0], rec.b[1], rec.b[2], lane);
+    uint32_t* out = words + (rec.offset - word0) + (uint32_t)brick_place(0, lane);  // + 64 x + 512 plane
+    int plane = 0;
+    // one plane of a 4-byte array: 8 loads, then 8 stores
+    auto plane4 = [&](uint32_t* arr, uint32_t fill) {
+        uint32_t v[kBrickRuns];
+        if (GATHER) {
+#pragma unroll
+            for (int x = 0; x < kBrickRuns; ++x) v[x] = arr[L.t[x]];
+#pragma unroll
+            for (int x = 0; x < kBrickRuns; ++x) out[plane * kBrickVoxels + 64 * x] = (L.real >> x) & 1u ? v[x] : fill;
+        } else {
+#pragma unroll
+            for (int x = 0; x < kBrickRuns; ++x) v[x] = out[plane * kBrickVoxels + 64 * x];
+#pragma unroll
+            for (int x = 0; x < kBrickRuns; ++x)
+                if ((L.real >> x) & 1u) arr[L.t[x]] = v[x];
+        }
+        ++plane;
+    };
+    plane4(reinterpret_cast<uint32_t*>(b.sdf), __float_as_uint(g.mu));
+    if (WT_WIDE) {
+        plane4(static_cast<uint32_t*>(b.wt), 0u);
+    } else {
+        uint16_t* wt = static_cast<uint16_t*>(b.wt);
+        uint32_t v[kBrickRuns];
+#pragma unroll
+        for (int x = 0; x < kBrickRuns; ++x) v[x] = GATHER ? (uint32_t)wt[L.t[x]] : out[plane * kBrickVoxels + 64 * x];
+#pragma unroll
+        for (int x = 0; x < kBrickRuns; ++x) {
+            if (GATHER) out[plane * kBrickVoxels + 64 * x] = (L.real >> x) & 1u ? v[x] : 0u;
+            else if ((L.real >> x) & 1u) wt[L.t[x]] = (uint16_t)v[x];
+        }
+        ++plane;
+    }
+    // colour: the 8 runs' values into registers first (three record planes each, or one), then the stores
+    if (COL_WIDE) {  // three planes <-> int32 x 4
+        int4* col = static_cast<int4*>(b.color);
+        int4 c[kBrickRuns];
+#pragma unroll
+        for (int x = 0; x < kBrickRuns; ++x) {
+            const uint32_t* o = out + plane * kBrickVoxels + 64 * x;
+            c[x] = GATHER ? col[L.t[x]] : make_int4((int)o[0], (int)o[kBrickVoxels], (int)o[2 * kBrickVoxels], 0);
+        }
+#pragma unroll
+        for (int x = 0; x < kBrickRuns; ++x) {
+            uint32_t* o = out + plane * kBrickVoxels + 64 * x;
+            const bool real = (L.real >> x) & 1u;
+            if (GATHER) {
+                o[0] = real ? (uint32_t)c[x].x : 0u;
+                o[kBrickVoxels] = real ? (uint32_t)c[x].y : 0u;
+                o[2 * kBrickVoxels] = real ? (uint32_t)c[x].z : 0u;
+            } else if (real) {
+                col[L.t[x]] = c[x];
+            }
+        }
+        plane += 3;
+    } else {  // u8 x 4 storage: one packed plane, or the three planes of a COLOR_I32 volume (values 0..255)
+        uint32_t* col = static_cast<uint32_t*>(b.color);
+        uint32_t c[kBrickRuns];
+#pragma unroll
+        for (int x = 0; x < kBrickRuns; ++x) {
+            const uint32_t* o = out + plane * kBrickVoxels + 64 * x;
+            if (GATHER) c[x] = col[L.t[x]] & 0x00FFFFFFu;
+            else c[x] = color_i32 ? (o[0] & 0xFFu) | (o[kBrickVoxels] & 0xFFu) << 8 | (o[2 * kBrickVoxels] & 0xFFu) << 16
+                                  : o[0] & 0x00FFFFFFu;
+        }
+#pragma unroll
+        for (int x = 0; x < kBrickRuns; ++x) {
+            uint32_t* o = out + plane * kBrickVoxels + 64 * x;
+            const bool real = (L.real >> x) & 1u;
+            if (GATHER) {
+                const uint32_t v = real ? c[x] : 0u;
+                if (color_i32) {
+                    o[0] = v & 0xFFu;
+                    o[kBrickVoxels] = (v >> 8) & 0xFFu;
+                    o[2 * kBrickVoxels] = v >> 16;
+                } else {
+                    o[0] = v;
+                }
+            } else if (real) {
+                col[L.t[x]] = c[x];
+            }
+        }
+        plane += color_i32 ? 3 : 1;
+    }
+    if (b.hist) {
+        if (GATHER) {
+            for (uint32_t m = rec.bins; m; m &= m - 1) plane4(b.hist + (uint64_t)(__ffs((int)m) - 1) * g.nvox, 0u);
+        } else {
+            uint32_t mask[kBrickRuns] = {};
+            for (int k = 0; k < kMaxObjects; ++k) {
+                uint32_t* arr = b.hist + (uint64_t)k * g.nvox;
+                const bool has = (rec.bins >> k) & 1u;  // wave-uniform
+                uint32_t v[kBrickRuns];
+#pragma unroll
+                for (int x = 0; x < kBrickRuns; ++x) v[x] = has ? out[plane * kBrickVoxels + 64 * x] : 0u;
+#pragma unroll
+                for (int x = 0; x < kBrickRuns; ++x) {
+                    if ((L.real >> x) & 1u) arr[L.t[x]] = v[x];
+                    mask[x] |= (v[x] != 0u ? 1u : 0u) << k;
+                }
+                if (has) ++plane;
+            }
+#pragma unroll
+            for (int x = 0; x < kBrickRuns; ++x)
+                if ((L.real >> x) & 1u) b.hmask[L.t[x]] = mask[x];
+        }
+    }
+    if (b.cls) {
+        plane4(reinterpret_cast<uint32_t*>(b.cls), 0u);
+        plane4(reinterpret_cast<uint32_t*>(b.cls_cnt), 0u);
+    }
+    if (!GATHER && (lane & 31) == 0) {
+#pragma unroll
+        for (int x = 0; x < kBrickRuns; ++x)
+            if ((L.exists >> x) & 1u) b.sflag[L.t[x] >> 5] = 0;
+    }
+}
+
+hipError_t launch_brick_records(bool gather, const VolGeom& g, const VolBufs& b, int color_wide, int color_i32,
+                                const BrickRec* list, uint64_t n, uint64_t word0, uint32_t* words, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const uint64_t blocks = (n + 3) / 4;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 gr((unsigned)blocks), bl(256);
+#define SEMTSDF_REC_LAUNCH(G, W, C) \
+    hipLaunchKernelGGL((k_brick_records<G, W, C>), gr, bl, 0, s, g, b, color_i32, list, n, word0, words)
+#define SEMTSDF_REC_FORMS(G)                                                                                       \
+    if (b.wt_wide) { if (color_wide) SEMTSDF_REC_LAUNCH(G, true, true); else SEMTSDF_REC_LAUNCH(G, true, false); } \
+    else { if (color_wide) SEMTSDF_REC_LAUNCH(G, false, true); else SEMTSDF_REC_LAUNCH(G, false, false); }
+    if (gather) { SEMTSDF_REC_FORMS(true) } else { SEMTSDF_REC_FORMS(false) }
+#undef SEMTSDF_REC_FORMS
+#undef SEMTSDF_REC_LAUNCH
+    return hipGetLastError();
+}
+
 }  // namespace semtsdf

@@ -11,7 +11,8 @@ from .config import Configuration, FusionConfig
 from .export import (export_surface, extract_mesh, merge_meshes, read_mesh_ply, read_ply, write_mesh_ply,
                      write_ply)
 from .instances import find_duplicates, instance_stats, merge_instance_stats, plan_remap
-from . import follow, maps, track
+from . import bricks, follow, maps, track
+from .bricks import BrickStore, shift_paged
 from .follow import evicted_points, plan_shift
 from .maps import pose_camera, shade_normals, z_depth
 from .track import TrackingLost
@@ -23,5 +24,5 @@ __all__ = ["TSDF", "Volume", "DeviceBuffer", "Configuration", "FusionConfig", "S
            "extract_mesh", "merge_meshes", "write_mesh_ply", "read_mesh_ply",
            "instance_stats", "merge_instance_stats", "find_duplicates", "plan_remap",
            "maps", "pose_camera", "z_depth", "shade_normals", "track", "TrackingLost",
-           "follow", "plan_shift", "evicted_points",
+           "follow", "plan_shift", "evicted_points", "bricks", "BrickStore", "shift_paged",
            "RENDER_LABEL", "RENDER_COLOR", "RAY_ASSOC", "PLACE_SFM", "PLACE_PYTHON"]

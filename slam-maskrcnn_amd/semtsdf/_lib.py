@@ -116,6 +116,16 @@ class Instance(C.Structure):
                 ("rgb_sum", C.c_uint64 * 3), ("min", C.c_uint32 * 3), ("max", C.c_uint32 * 3)]
 
 
+class Brick(C.Structure):
+    """semtsdf_brick: a brick of a packed box, its histogram bins and the word offset of its record."""
+    _fields_ = [("b", C.c_int32 * 3), ("bins", C.c_uint32), ("offset", C.c_uint64)]
+
+
+# the same 24 bytes as a structured NumPy dtype (Volume.pack_bricks / unpack_bricks)
+BRICK_DTYPE = np.dtype([("b", np.int32, 3), ("bins", np.uint32), ("offset", np.uint64)])
+BRICK_VOXELS = 512
+
+
 class MapsOut(C.Structure):
     """semtsdf_maps_out: one pointer per map, NULL where the map is not requested."""
     _fields_ = [("t", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("label", C.c_void_p),
@@ -260,6 +270,9 @@ SIGNATURES = {
                                   C.POINTER(C.c_uint64)]),
     "semtsdf_instance_stats": (_I, [_P, _F, C.c_int32, _P, _P]),
     "semtsdf_remap_instances": (_I, [_P, _P, C.c_int32, _P]),
+    "semtsdf_pack_bricks": (_I, [_P, _P, _P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64),
+                                 C.POINTER(C.c_uint64)]),
+    "semtsdf_unpack_bricks": (_I, [_P, _P, C.c_uint64, _P, C.c_uint64]),
     "semtsdf_map_words": (_I, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "semtsdf_set_instrumentation": (_I, [_P, _I]),
     "semtsdf_get_timing": (_I, [_P, C.POINTER(Timing)]),

@@ -61,6 +61,7 @@ class TSDF:
         self.last_assoc: L.AssocStats | None = None
         self.last_extrinsic = None   # W2C of the last fused frame: TSDF.track's default guess
         self.last_track = None       # per-iteration log of the last TSDF.track
+        self.store = None            # the BrickStore of the last paged follow (TSDF.follow(store=...))
 
     # ------------------------------------------------------------------ placement (a1)
     def _flags(self) -> int:
@@ -158,14 +159,17 @@ class TSDF:
         return st
 
     def follow(self, extrinsic, focus_depth=None, trigger_bricks: int = 2, on_evict=None, sdf_max: float = 0.2,
-               min_weight: int = 1):
+               min_weight: int = 1, store=None):
         """Recentre the volume on what the camera at `extrinsic` (W2C, as parse_frame takes it)
         looks at, `focus_depth` metres ahead (by default the mean depth of the first frame):
         semtsdf.follow.plan_shift decides, Volume.shift moves the voxels by whole bricks on the
         device, vol_start / vol_end follow.  Returns the shift (sx, sy, sz) in voxels, or None when
         none was due (or nothing is placed yet).  on_evict, if given, is called before the shift
         with the surface points about to leave (semtsdf.follow.evicted_points with sdf_max and
-        min_weight).  Intended use: t.follow(pose); t.parse_frame(..., pose, ...)."""
+        min_weight).  With `store` (a semtsdf.bricks.BrickStore) the shift is paged
+        (semtsdf.bricks.shift_paged): the occupied bricks that leave are kept in the store, those of
+        the store that the volume covers again come back, and the store is remembered for
+        prune_instances.  Intended use: t.follow(pose); t.parse_frame(..., pose, ...)."""
         from .follow import evicted_points, plan_shift
 
         if not self.init or self.vol is None:
@@ -176,9 +180,19 @@ class TSDF:
                            self.mean_depth if focus_depth is None else focus_depth, trigger_bricks)
         if shift is None:
             return None
+        if store is not None:  # a store that cannot page for this volume is refused before anything happens
+            from .bricks import check_paged
+
+            check_paged(self.vol, store)
         if on_evict is not None:
             on_evict(evicted_points(self.vol, shift, sdf_max, min_weight))
-        self.vol.shift(*shift)
+        if store is not None:
+            from .bricks import shift_paged
+
+            shift_paged(self.vol, store, shift)
+            self.store = store  # remembered once it has paged for this volume
+        else:
+            self.vol.shift(*shift)
         p = self.vol.params
         self.vol_start = np.array(p.vol_start[:], dtype=np.asarray(self.vol_start).dtype)
         self.vol_end = np.array(p.vol_end[:], dtype=np.asarray(self.vol_end).dtype)
@@ -263,6 +277,8 @@ class TSDF:
         st = self.vol.instance_stats(sdf_max, min_weight, overlap=True)
         lut, num = plan_remap(st, self.num_objs, duplicate_thresh=thr, min_voxels=min_voxels, compact=True)
         self.vol.remap_instances(lut, num)
+        if self.store is not None:  # the bricks paged out carry the same ids
+            self.store.remap(lut)
         return lut, num
 
     # ------------------------------------------------------------------ raycast (a8)

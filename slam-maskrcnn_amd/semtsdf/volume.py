@@ -528,6 +528,37 @@ class Volume:
                 c(cls, np.int32), c(cls_cnt, np.int32)]
         L.check(L.load().semtsdf_upload(self._h, *[L.ptr(a) for a in arrs]))
 
+    # ---- brick paging (semtsdf/bricks.py drives these)
+    def brick_counts(self):
+        """(nbx, nby, nbz): the 8^3 bricks per axis, ceil(dim / 8)."""
+        return tuple((int(d) + 7) // 8 for d in self.local_dim)
+
+    def pack_bricks(self, lo=None, hi=None):
+        """The occupied bricks of the brick box lo <= b < hi (default: the whole volume) as
+        (bricks, words): a structured array (b i32 x 3, bins u32, offset u64) in ascending
+        (bx, by, bz) order and the u32 words of their records back to back (semtsdf_pack_bricks:
+        a count call, then a fill call)."""
+        lo = np.array([0, 0, 0] if lo is None else lo, np.int32).reshape(3)
+        hi = np.array(self.brick_counts() if hi is None else hi, np.int32).reshape(3)
+        nb, nw = C.c_uint64(0), C.c_uint64(0)
+        fn = L.load().semtsdf_pack_bricks
+        L.check(fn(self._h, L.ptr(lo), L.ptr(hi), None, 0, None, 0, C.byref(nb), C.byref(nw)))
+        bricks = np.zeros(nb.value, L.BRICK_DTYPE)
+        words = np.zeros(nw.value, np.uint32)
+        if nb.value:
+            L.check(fn(self._h, L.ptr(lo), L.ptr(hi), C.c_void_p(bricks.ctypes.data), nb.value,
+                       C.c_void_p(words.ctypes.data), nw.value, C.byref(nb), C.byref(nw)))
+        return bricks, words
+
+    def unpack_bricks(self, bricks, words):
+        """Overwrites the listed bricks with their records (semtsdf_unpack_bricks): `bricks` and
+        `words` as pack_bricks returns them, of this volume or of one with the same flags."""
+        bricks = np.ascontiguousarray(bricks, L.BRICK_DTYPE).reshape(-1)
+        words = np.ascontiguousarray(words, np.uint32).reshape(-1)
+        L.check(L.load().semtsdf_unpack_bricks(self._h, C.c_void_p(bricks.ctypes.data) if bricks.size else None,
+                                               bricks.size, C.c_void_p(words.ctypes.data) if words.size else None,
+                                               words.size))
+
     # ---- instance inventory and id remapping
     def instance_stats(self, sdf_max: float = 0.2, min_weight: int = 1, overlap: bool = True) -> dict:
         """Per-instance voxel counts, votes, supports, index and colour sums, boxes and the
